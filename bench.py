@@ -2,7 +2,7 @@
 """Headline benchmark: ResNet-50 amp O2 (bf16) training throughput, images/sec
 for the whole job (BASELINE.json metric), 1..8 MI355X, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [...]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Without torchrun (WORLD_SIZE unset) and --gpus N > 1, bench.py starts the N
@@ -18,6 +18,16 @@ fp32 master weights, bf16 model copy written in-kernel).  Synthetic ImageNet
 shaped data (224x224, 1000 classes) generated on the device per rank;
 random-init weights.  W untimed warmup steps, then exactly K timed steps
 bracketed by barrier + synchronize; the slowest rank's time is reported.
+
+A plain run does only that: set up, warm up, time the K steps, check that they were
+real training steps (no step skipped by the loss scaler; at N > 1 the replicas still
+bitwise in sync), print one JSON line.  ``--dump-outputs DIR`` also writes what the last
+timed step computed (its loss, its logits where the step keeps them, and the model's
+parameters and buffers after it) as float32 ``DIR/<name>.npy``; the seeds are fixed, so
+two builds run with the same arguments see identical inputs.  ``--full`` adds the
+secondary measurements, each a run of its own after the timed steps: the optimizer step
+alone (``optimizer_step_ms`` / ``optimizer_step_host_ms``) and, at N > 1 or with
+``--force-collectives``, the per-bucket DDP / SyncBN timing block (``ddp``).
 
 Other BASELINE.json configs (same harness):
   --model bert_large   BERT-large pretraining, amp O2 + FusedLAMB + FusedLayerNorm
@@ -105,7 +115,17 @@ def parse():
     # MI355X (docs/PERF.md) and avoids ~200 s of solver search on a fresh box.
     ap.add_argument("--cudnn-benchmark", action="store_true",
                     help="MIOpen find (solver search) instead of immediate mode")
-    ap.add_argument("--opt-step-iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: the "
+                         "optimizer step alone (--opt-step-iters) and, at N > 1 or with "
+                         "--force-collectives, the per-bucket DDP timing "
+                         "(--bucket-timing-steps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, logits where kept, "
+                         "parameters and buffers after it; a fixed seeded sample when larger "
+                         "than 64 MB in all) as float32 DIR/<name>.npy")
+    ap.add_argument("--opt-step-iters", type=int, default=20,
+                    help="--full: iterations of the optimizer-step-alone timing")
     ap.add_argument("--pg-timeout", type=int, default=300,
                     help="process-group timeout, seconds: a collective hang at N ranks fails "
                          "within this instead of the 30-minute default")
@@ -122,7 +142,7 @@ def parse():
                          "critical-path kernels win the CUs over the side-stream weight "
                          "gradients")
     ap.add_argument("--bucket-timing-steps", type=int, default=5,
-                    help="N > 1: extra untimed steps with per-bucket DDP timing (0 = off)")
+                    help="--full, N > 1: extra untimed steps with per-bucket DDP timing (0 = off)")
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--loss-trace", action="store_true",
                     help="keep every step's loss (device scalars, read after timing) in the JSON")
@@ -131,7 +151,10 @@ def parse():
                          "whose dynamic scale is still settling)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + rendezvous + world-size check only (launcher tests)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -244,6 +267,7 @@ def build_resnet(args, device, world):
     x = torch.randn(bs, 3, args.image_size, args.image_size, device=device).to(memory_format=mf)
     y = torch.randint(0, 1000, (bs,), device=device)
     w = Workload()
+    keep_logits = bool(args.dump_outputs)
     if args.impl == "amd":
         opt = FusedSGD(model.parameters(), lr=lr, momentum=0.9, weight_decay=5e-5,
                        materialize_master_grads=args.materialize_master_grads)
@@ -257,6 +281,8 @@ def build_resnet(args, device, world):
 
         def step(b):
             out = model(b[0])
+            if keep_logits:  # --dump-outputs: a detached alias, no kernel
+                w.last_logits = out.detach()
             loss = F.cross_entropy(out, b[1])
             opt.zero_grad()
             with amp.scale_loss(loss, opt) as scaled:
@@ -594,6 +620,61 @@ def ddp_timing(ddp, step, batch, steps, device):
     return rec
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # parameters + buffers; loss and logits come on top (< 64 MB in all)
+
+
+def _sampled_flat(tensors, budget_elems):
+    """The tensors flattened to float32 and concatenated in order.  When they hold more
+    than ``budget_elems`` elements in all, small tensors stay whole and every tensor
+    larger than an equal share of what they leave is represented by a fixed, seeded
+    sample of that many of its elements (same indices on every run)."""
+    tensors = [t.detach() for t in tensors]
+    share, left = None, budget_elems
+    if sum(t.numel() for t in tensors) > budget_elems:
+        sizes = sorted(t.numel() for t in tensors)
+        for i, n in enumerate(sizes):
+            share = max(1, left // (len(sizes) - i))
+            if n > share:
+                break
+            left -= n
+    g = torch.Generator().manual_seed(20240229)
+    parts = []
+    for t in tensors:
+        flat = t.reshape(-1)
+        if share is not None and flat.numel() > share:
+            idx = torch.randint(0, flat.numel(), (share,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts).numpy() if parts else None
+
+
+def dump_outputs(out_dir, w, loss):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step, as
+    float32 .npy files: the loss it returned, the logits it computed (workloads whose step
+    keeps them), and the model it trained (parameters and buffers; sampled when large)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    model = w.model.module if hasattr(w.model, "module") else w.model
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    logits = getattr(w, "last_logits", None)
+    if logits is not None and logits.numel() * 4 <= (8 << 20):
+        arrays["logits"] = logits.float().cpu().numpy()
+    budget = DUMP_BUDGET_BYTES // 4
+    params = _sampled_flat(list(model.parameters()), budget * 3 // 4)
+    if params is not None:
+        arrays["params"] = params
+    bufs = _sampled_flat([b for b in model.buffers() if b.is_floating_point()], budget // 4)
+    if bufs is not None:
+        arrays["buffers"] = bufs
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     args = parse()
     if args.message_size != "auto":
@@ -731,21 +812,28 @@ def main():
         skipped = int(t.item())
     scale_now = _loss_scale(args)
 
-    # optimizer step alone (secondary metric of BASELINE.json)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    h0 = time.perf_counter()
-    for _ in range(args.opt_step_iters):
-        w.opt_only()
-    opt_host_ms = (time.perf_counter() - h0) * 1e3 / args.opt_step_iters  # launch side only
-    e1.record()
-    torch.cuda.synchronize()
-    opt_ms = e0.elapsed_time(e1) / args.opt_step_iters
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything below runs the optimizer or the step again
+        dumped = dump_outputs(args.dump_outputs, w, loss)
+
+    opt_ms = opt_host_ms = None
+    if args.full and args.opt_step_iters > 0:
+        # optimizer step alone (secondary metric of BASELINE.json)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        h0 = time.perf_counter()
+        for _ in range(args.opt_step_iters):
+            w.opt_only()
+        opt_host_ms = (time.perf_counter() - h0) * 1e3 / args.opt_step_iters  # launch side only
+        e1.record()
+        torch.cuda.synchronize()
+        opt_ms = e0.elapsed_time(e1) / args.opt_step_iters
 
     ddp_stats = None
     ddp = getattr(w, "ddp", None)
-    if ((world > 1 or args.force_collectives) and ddp is not None
+    if (args.full and (world > 1 or args.force_collectives) and ddp is not None
             and args.bucket_timing_steps > 0):
         ddp_stats = ddp_timing(ddp, step, batch, args.bucket_timing_steps, device)
 
@@ -778,14 +866,18 @@ def main():
         "dtype": w.dtype,
         "data": w.data,
         "config": w.config,
-        "optimizer_step_ms": round(opt_ms, 4),
-        "optimizer_step_host_ms": round(opt_host_ms, 4),
+        "full": bool(args.full),
+        # --full only (None in a plain run)
+        "optimizer_step_ms": round(opt_ms, 4) if opt_ms is not None else None,
+        "optimizer_step_host_ms": round(opt_host_ms, 4) if opt_host_ms is not None else None,
         "final_loss": round(final_loss, 4),
         "skipped_steps": skipped,
         "loss_scale": scale_now,
         "launcher": os.environ.get("APEX_AMD_BENCH_LAUNCHER",
                                    "torchrun" if world > 1 else "single"),
     }
+    if dumped is not None:
+        rec["dumped_outputs"] = dumped
     if ddp_stats is not None:
         rec["ddp"] = ddp_stats
     if consistency is not None:

@@ -344,7 +344,7 @@ def test_bench_self_spawn_two_ranks_one_gpu():
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--model", "resnet18", "--batch-size", "16", "--image-size", "64",
-                        "--steps", "3", "--warmup", "2", "--bucket-timing-steps", "2",
+                        "--steps", "3", "--warmup", "2", "--full", "--bucket-timing-steps", "2",
                         "--opt-step-iters", "2"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -372,7 +372,7 @@ def test_bench_two_ranks_desynced_replica_fails():
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--model", "resnet18", "--batch-size", "8", "--image-size", "32",
-                        "--steps", "2", "--warmup", "1", "--bucket-timing-steps", "0",
+                        "--steps", "2", "--warmup", "1", "--full", "--bucket-timing-steps", "0",
                         "--opt-step-iters", "1"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 5, p.stdout[-2000:] + p.stderr[-4000:]
@@ -399,7 +399,7 @@ def test_bench_transformers_two_ranks_one_gpu(model):
     shape = ["--batch-size", "2", "--seq-len", "128"] if model == "bert_large" else \
         ["--batch-size", "1", "--seq-len", "256", "--allow-skipped-steps"]
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
-                        "--model", model, "--steps", "2", "--warmup", "2",
+                        "--model", model, "--steps", "2", "--warmup", "2", "--full",
                         "--bucket-timing-steps", "1", "--opt-step-iters", "1",
                         "--message-size", str(8 << 20)] + shape,
                        env=env, capture_output=True, text=True, timeout=260)

@@ -129,3 +129,45 @@ def test_bench_refuses_world_mismatch():
                         "--dry-run"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 3
     assert "refusing" in p.stderr
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files; a model above the budget is represented
+    by the same seeded element sample on every call, small tensors whole, and the total
+    stays below the budget."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Wl:
+        pass
+
+    torch.manual_seed(3)
+    w = Wl()
+    w.model = torch.nn.Sequential(torch.nn.Linear(301, 299), torch.nn.BatchNorm1d(299)).bfloat16()
+    w.last_logits = torch.randn(5, 7).bfloat16()
+    loss = torch.tensor(1.25, dtype=torch.bfloat16)
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), w, loss)
+    n_par = sum(p.numel() for p in w.model.parameters())
+    assert shapes == {"loss": [1], "logits": [5, 7], "params": [n_par], "buffers": [2 * 299]}
+    par = np.load(tmp_path / "whole" / "params.npy")
+    assert par.dtype == np.float32
+    want = torch.cat([p.detach().reshape(-1).float() for p in w.model.parameters()]).numpy()
+    assert np.array_equal(par, want)
+    assert np.load(tmp_path / "whole" / "loss.npy").tolist() == [1.25]
+    assert np.array_equal(np.load(tmp_path / "whole" / "logits.npy"), w.last_logits.float().numpy())
+
+    bench.DUMP_BUDGET_BYTES = 4 * 40000   # 30,000 parameter elements: 3 x 299 whole, the rest sampled
+    a = bench.dump_outputs(str(tmp_path / "a"), w, loss)
+    b = bench.dump_outputs(str(tmp_path / "b"), w, loss)
+    assert a == b and a["params"] == [30000]
+    pa, pb = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "b" / "params.npy")
+    assert np.array_equal(pa, pb)
+    assert np.array_equal(pa[30000 - 3 * 299:], want[301 * 299:])        # the small tensors, whole
+    assert np.isin(pa[:30000 - 3 * 299], want[:301 * 299]).all()         # sampled from the weight
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total < bench.DUMP_BUDGET_BYTES

@@ -50,9 +50,35 @@ def test_reference_program_on_gpu(tmp_path, extra):
 def test_bench_convnet(opt):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "convnet",
                         "--steps", "20", "--warmup", "10", "--convnet-optimizer", opt,
-                        "--opt-step-iters", "2"],
+                        "--full", "--opt-step-iters", "2"],
                        capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     rec = json.loads(p.stdout.strip().splitlines()[-1])
     assert rec["config"]["model"] == "convnet" and rec["dtype"] == "fp16"
     assert rec["skipped_steps"] == 0 and rec["epoch_seconds"] > 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps steps, reports ms_per_step consistent with its
+    value, leaves the --full measurements out, and --dump-outputs writes the last timed
+    step's loss and the trained model as finite float32 arrays."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--model", "convnet", "--steps", "7", "--warmup", "3", "--loss-trace",
+                        "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    rec = json.loads(p.stdout.strip().splitlines()[-1])
+    assert rec["steps"] == 7 and len(rec["loss_trace"]) == 3 + 7
+    assert rec["full"] is False and rec["optimizer_step_ms"] is None and "ddp" not in rec
+    per_step = rec["config"]["global_batch"] / rec["value"] * 1e3
+    assert abs(per_step - rec["ms_per_step"]) <= 0.01 * rec["ms_per_step"] + 1e-3
+    assert sorted(os.listdir(out)) == ["buffers.npy", "loss.npy", "params.npy"]
+    assert set(rec["dumped_outputs"]) == {"buffers", "loss", "params"}
+    assert np.load(out / "buffers.npy").shape == (2 * (16 + 32),)    # BN running mean / var
+    loss, par = np.load(out / "loss.npy"), np.load(out / "params.npy")
+    assert loss.dtype == np.float32 and par.dtype == np.float32
+    assert abs(float(loss[0]) - rec["final_loss"]) < 1e-3
+    assert par.size == rec["dumped_outputs"]["params"][0] > 1000 and np.isfinite(par).all()
