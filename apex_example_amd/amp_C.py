@@ -220,7 +220,7 @@ def multi_tensor_novograd(chunk_size, noop_flag, tensor_lists, grad_norms, lr, b
     else:
         step_v, step_t = int(step), None
     # first_step=True with grad_norms == v makes the in-kernel blend the identity
-    _C().novograd(noop_flag, tensor_lists, grad_norms, grad_norms, True, lv, lt, float(beta1),
+    _C().novograd(noop_flag, tensor_lists, grad_norms, grad_norms, True, None, lv, lt, float(beta1),
                   float(beta2), float(epsilon), step_v, step_t, bool(bias_correction),
                   float(weight_decay), bool(grad_averaging), int(mode), int(norm_type), sv, st,
                   scale_inv)

@@ -54,6 +54,12 @@ class FusedNovoGrad(FusedOptimizerBase):
             first = "exp_avg_sq" not in group
             if first:
                 group["exp_avg_sq"] = []
+            # sync-free: the device may skip this step (overflow), and a skipped first step
+            # must not consume the seed - "v is seeded" then lives in a device flag
+            # (0 => seed), marked done only by a step that ran, like FusedSGD's first run
+            flag = None
+            if not group["init_zero"] and self._sync_free() and dev.type == "cuda":
+                flag = self._dev_flag((gid, "seeded"), dev, first)
             for k, (key, s) in enumerate(sets.items()):
                 m, = self._state_lists(s, ("exp_avg",))
                 _, gnorms = C.norm(scratch, s["grads"], True, group["norm_type"] == 0)
@@ -69,7 +75,8 @@ class FusedNovoGrad(FusedOptimizerBase):
                 lists = [s["grads"], s["params"], m]
                 lv = group["lr"]
                 sv, st = (1.0, scale_v) if isinstance(scale_v, torch.Tensor) else (float(scale_v), None)
-                C.novograd(noop, lists, v, gnorms, bool(first_blend), float(lv), None, float(beta1),
+                C.novograd(noop, lists, v, gnorms, bool(first_blend), flag, float(lv), None,
+                           float(beta1),
                            float(beta2), float(group["eps"]), int(step), step_t,
                            bool(bias_correction), float(group["weight_decay"]),
                            bool(grad_averaging), int(self.moment_mode), int(group["norm_type"]),
@@ -78,5 +85,7 @@ class FusedNovoGrad(FusedOptimizerBase):
                     from .. import amp_C
 
                     amp_C.multi_tensor_scale(65536, scratch, [s["params"], s["copies"]], 1.0)
+            if flag is not None:
+                C.mark_step_done(flag, noop)
             self._after_step(gid, dev, step_t, noop)
         return loss

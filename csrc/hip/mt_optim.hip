@@ -135,7 +135,8 @@ bool mt_sgd_pair(const MTLaunch& A, DType ga, DType pa, DType ca, const SgdArgs&
 void mt_sgd(const MTLaunch& L, int depth, DType g, DType p, DType m, DType copy, const SgdArgs& a,
             const int* noop, hipStream_t st) {
   if (L.nchunks == 0) return;
-  // momentum buffers always share the parameter dtype (zeros_like(p))
+  // momentum buffers share the parameter dtype (zeros_like(p)); the torch-facing op and
+  // the StepPlan reject any other pairing before they get here
   (void)m;
   dispatch1(g, [&](auto tg) {
     dispatch1(p, [&](auto tp) {
@@ -527,10 +528,12 @@ void mt_lamb_stage2(const MTLaunch& L, int depth, DType p, DType copy, const Lam
 // --------------------------------------------------------------------------
 // NovoGrad: per-tensor second moment kept as a norm
 __global__ void novograd_blend_kernel(float* v, const float* gn, int n, float beta2, int norm_type,
-                                      int first_step, const int* noop) {
+                                      int first_step, const int* first_step_flag,
+                                      const int* noop) {
   if (skip_step(noop)) return;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (first_step_flag) first_step = (*first_step_flag == 0);
   float g = gn[i];
   if (first_step) {
     v[i] = g;
@@ -542,10 +545,10 @@ __global__ void novograd_blend_kernel(float* v, const float* gn, int n, float be
 }
 
 void novograd_blend(float* v, const float* grad_norms, int ntensors, float beta2, int norm_type,
-                    int first_step, const int* noop, hipStream_t st) {
+                    int first_step, const int* first_step_flag, const int* noop, hipStream_t st) {
   if (ntensors == 0) return;
   hipLaunchKernelGGL(novograd_blend_kernel, dim3((ntensors + 255) / 256), dim3(256), 0, st, v,
-                     grad_norms, ntensors, beta2, norm_type, first_step, noop);
+                     grad_norms, ntensors, beta2, norm_type, first_step, first_step_flag, noop);
 }
 
 template <typename TG, typename TP>

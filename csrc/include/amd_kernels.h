@@ -131,8 +131,10 @@ struct NovoArgs {
 // `grad_norms` holds this step's per-tensor grad norms; v is blended in-kernel
 // by the first chunk of each tensor only after every chunk has read it -> the
 // blend is done by a separate tiny kernel (novograd_blend) before the update.
+// first_step seeds v with the grad norm instead of blending; an optional device flag
+// overrides it (first_step = (*flag == 0), set by mark_step_done after a step that ran).
 void novograd_blend(float* v, const float* grad_norms, int ntensors, float beta2, int norm_type,
-                    int first_step, const int* noop, hipStream_t st);
+                    int first_step, const int* first_step_flag, const int* noop, hipStream_t st);
 void mt_novograd(const MTLaunch& L, DType g, DType p, const NovoArgs& a, const float* v,
                  const int* noop, hipStream_t st);
 

@@ -201,6 +201,8 @@ void mt_sgd_op(at::Tensor noop, const TensorLists& lists, double wd, double mome
   a.lr_ptr = opt_fptr(lr_t);
   a.first_run_flag = opt_iptr(first_run_flag);
   by_dtype_groups(lists, [&](const std::vector<int>&, const TensorLists& g) {
+    TORCH_CHECK(g[2][0].scalar_type() == g[1][0].scalar_type(),
+                "sgd: momentum must match the parameter dtype");
     const MTPlan& P = mt_plan(g);
     DType copy = g.size() == 4 ? dtype_of(g[3][0]) : dtype_of(g[1][0]);
     mt_sgd(P.L, (int)g.size(), dtype_of(g[0][0]), dtype_of(g[1][0]), dtype_of(g[2][0]), copy, a,
@@ -216,6 +218,7 @@ void mt_adam_op(at::Tensor noop, const TensorLists& lists, double lr, c10::optio
   if (lists.empty() || lists[0].empty()) return;
   bool gpu = mt_validate(lists, 4, 5);
   if (!gpu) {
+    TORCH_CHECK(!lr_t.has_value() || !lr_t->defined(), "device lr only on GPU");
     cpu::Adam a{(float)lr, (float)beta1, (float)beta2, (float)eps, (float)wd, (int)step,
                 optp(step_t), (int)mode, bias_correction ? 1 : 0, cscale(scale, scale_t, scale_inv)};
     return cpu::adam(noop, lists, a);
@@ -255,6 +258,7 @@ void mt_lamb_op(at::Tensor noop, const TensorLists& lists, double lr, c10::optio
   // stage 2 from (p, m, v) - no fp32 workspace
   bool gpu = mt_validate(lists, 4, 5);
   if (!gpu) {
+    TORCH_CHECK(!lr_t.has_value() || !lr_t->defined(), "device lr only on GPU");
     cpu::Lamb a{(float)lr, (float)beta1, (float)beta2, (float)eps, (float)wd, (int)step,
                 optp(step_t), (int)mode, bias_correction ? 1 : 0, grad_averaging ? 1 : 0,
                 optp(global_grad_norm), (float)max_grad_norm, use_nvlamb,
@@ -356,22 +360,36 @@ void mt_lamb_legacy_stage2_op(at::Tensor noop, const TensorLists& lists, at::Ten
 }
 
 void mt_novograd_op(at::Tensor noop, const TensorLists& lists, at::Tensor v, at::Tensor grad_norms,
-                    bool first_step, double lr, c10::optional<at::Tensor> lr_t, double beta1,
-                    double beta2, double eps, int64_t step, c10::optional<at::Tensor> step_t,
-                    bool bias_correction, double wd, bool grad_averaging, int64_t mode,
-                    int64_t norm_type, double scale, c10::optional<at::Tensor> scale_t,
-                    bool scale_inv) {
+                    bool first_step, c10::optional<at::Tensor> first_step_flag, double lr,
+                    c10::optional<at::Tensor> lr_t, double beta1, double beta2, double eps,
+                    int64_t step, c10::optional<at::Tensor> step_t, bool bias_correction,
+                    double wd, bool grad_averaging, int64_t mode, int64_t norm_type, double scale,
+                    c10::optional<at::Tensor> scale_t, bool scale_inv) {
   c10::NoGradGuard no_grad_;  // optimizer / scaler state is never differentiated
   if (lists.empty() || lists[0].empty()) return;
   bool gpu = mt_validate(lists, 3, 3);
   if (!gpu) {
+    TORCH_CHECK(!lr_t.has_value() || !lr_t->defined(), "device lr only on GPU");
     cpu::Novo a{(float)lr, (float)beta1, (float)beta2, (float)eps, (float)wd, (int)step,
                 optp(step_t), (int)mode, bias_correction ? 1 : 0, grad_averaging ? 1 : 0,
                 (int)norm_type, cscale(scale, scale_t, scale_inv)};
+    if (at::Tensor* f = optp(first_step_flag)) first_step = f->item<int>() == 0;
     return cpu::novograd(noop, lists, v, grad_norms, first_step, a);
   }
   TORCH_CHECK(v.is_cuda() && v.scalar_type() == at::kFloat && v.numel() == (int64_t)lists[0].size(),
               "novograd: v must be a float32 device tensor with one entry per parameter");
+  TORCH_CHECK(grad_norms.is_cuda() && grad_norms.scalar_type() == at::kFloat &&
+                  grad_norms.numel() == v.numel() && grad_norms.is_contiguous() &&
+                  v.is_contiguous(),
+              "novograd: grad_norms must be a float32 device tensor with one entry per parameter");
+  // A single dtype group is required here because v is indexed by tensor position.
+  for (size_t i = 0; i < lists[0].size(); ++i) {
+    TORCH_CHECK(lists[0][i].scalar_type() == lists[0][0].scalar_type() &&
+                    lists[1][i].scalar_type() == lists[1][0].scalar_type(),
+                "novograd: one dtype per launch");
+    TORCH_CHECK(lists[2][i].scalar_type() == lists[1][i].scalar_type(),
+                "novograd: exp_avg must match the parameter dtype");
+  }
   NovoArgs a;
   a.lr = (float)lr;
   a.beta1 = (float)beta1;
@@ -388,15 +406,11 @@ void mt_novograd_op(at::Tensor noop, const TensorLists& lists, at::Tensor v, at:
   a.scale = make_scale(scale, scale_t, scale_inv);
   a.lr_ptr = opt_fptr(lr_t);
   // grad_norms are unscaled norms of the (scaled) grads -> fold scale in on host side by caller.
+  // first_step_flag (device, 0 until a step has run): "v is seeded" survives a skipped step
   novograd_blend(v.data_ptr<float>(), grad_norms.data_ptr<float>(), (int)v.numel(), a.beta2,
-                 a.norm_type, first_step ? 1 : 0, noop_ptr(noop), cur_stream());
-  // A single dtype group is required here because v is indexed by tensor position.
+                 a.norm_type, first_step ? 1 : 0, opt_iptr(first_step_flag), noop_ptr(noop),
+                 cur_stream());
   const MTPlan& P = mt_plan(lists);
-  for (size_t i = 1; i < lists[0].size(); ++i) {
-    TORCH_CHECK(lists[0][i].scalar_type() == lists[0][0].scalar_type() &&
-                    lists[1][i].scalar_type() == lists[1][0].scalar_type(),
-                "novograd: one dtype per launch");
-  }
   mt_novograd(P.L, dtype_of(lists[0][0]), dtype_of(lists[1][0]), a, v.data_ptr<float>(),
               noop_ptr(noop), cur_stream());
 }
@@ -408,6 +422,7 @@ void mt_adagrad_op(at::Tensor noop, const TensorLists& lists, double lr,
   if (lists.empty() || lists[0].empty()) return;
   bool gpu = mt_validate(lists, 3, 3);
   if (!gpu) {
+    TORCH_CHECK(!lr_t.has_value() || !lr_t->defined(), "device lr only on GPU");
     cpu::Adagrad a{(float)lr, (float)eps, (float)wd, (int)mode, cscale(scale, scale_t, scale_inv)};
     return cpu::adagrad(noop, lists, a);
   }
@@ -419,6 +434,8 @@ void mt_adagrad_op(at::Tensor noop, const TensorLists& lists, double lr,
   a.scale = make_scale(scale, scale_t, scale_inv);
   a.lr_ptr = opt_fptr(lr_t);
   by_dtype_groups(lists, [&](const std::vector<int>&, const TensorLists& g) {
+    TORCH_CHECK(g[2][0].scalar_type() == g[1][0].scalar_type(),
+                "adagrad: sum must match the parameter dtype");
     const MTPlan& P = mt_plan(g);
     mt_adagrad(P.L, dtype_of(g[0][0]), dtype_of(g[1][0]), a, noop_ptr(noop), cur_stream());
   });
@@ -453,6 +470,14 @@ StepPlan::StepPlan(std::vector<at::Tensor> owners, TensorLists fixed) : owners_(
   gptr_.assign(owners_.size(), nullptr);
   gtype_ = at::ScalarType::Undefined;
   gpu_ = lists_[1][0].is_cuda();
+  // one kernel instantiation per launch set: every fixed list has one dtype, and on the
+  // GPU one the kernels dispatch (the grads are checked when they are read, refresh())
+  for (size_t d = 1; d < lists_.size(); ++d)
+    for (const at::Tensor& t : lists_[d]) {
+      TORCH_CHECK(t.scalar_type() == lists_[d][0].scalar_type(),
+                  "StepPlan: one dtype per list of a launch set");
+      if (gpu_) check_kernel_dtype(t, "StepPlan");
+    }
 }
 
 bool StepPlan::refresh() {
@@ -600,6 +625,8 @@ bool StepPlan::sgd(at::Tensor noop, double wd, double momentum, double dampening
               first_run_flag, wd_after_momentum, scale, scale_t, scale_inv);
     return true;
   }
+  TORCH_CHECK(lists_[2][0].scalar_type() == lists_[1][0].scalar_type(),
+              "sgd: momentum must match the parameter dtype");
   SgdArgs a;
   a.wd = (float)wd;
   a.momentum = (float)momentum;
@@ -625,6 +652,9 @@ bool StepPlan::sgd_pair(StepPlan& o, at::Tensor noop, double wd, double momentum
   if (lists_.size() != 4 || o.lists_.size() != 3) return false;
   if (!refresh() || !o.refresh()) return false;
   if (!gpu_launch_ready() || !o.gpu_launch_ready()) return false;
+  TORCH_CHECK(lists_[2][0].scalar_type() == lists_[1][0].scalar_type() &&
+                  o.lists_[2][0].scalar_type() == o.lists_[1][0].scalar_type(),
+              "sgd: momentum must match the parameter dtype");
   auto args = [&](double sv, const OptT& st, bool inv) {
     SgdArgs a;
     a.wd = (float)wd;
@@ -657,6 +687,9 @@ bool StepPlan::adam(at::Tensor noop, double lr, OptT lr_t, double beta1, double 
     mt_adam_op(noop, lists_, lr, lr_t, beta1, beta2, eps, step, step_t, mode, bias_correction, wd,
                scale, scale_t, scale_inv);
   } else {
+    TORCH_CHECK(lists_[2][0].scalar_type() == lists_[1][0].scalar_type() &&
+                    lists_[3][0].scalar_type() == lists_[1][0].scalar_type(),
+                "adam: exp_avg / exp_avg_sq must match the parameter dtype");
     AdamArgs a;
     a.lr = (float)lr;
     a.beta1 = (float)beta1;
@@ -712,6 +745,8 @@ void flat_scale_op(at::Tensor in, at::Tensor out, double scale, c10::optional<at
     if (out.defined()) out.copy_(in.to(at::kFloat) * s);
     return;
   }
+  check_kernel_dtype(in, "flat_scale");
+  if (out.defined()) check_kernel_dtype(out, "flat_scale");
   flat_scale(in.data_ptr(), dtype_of(in), out.defined() ? out.data_ptr() : nullptr,
              out.defined() ? dtype_of(out) : dtype_of(in), in.numel(),
              make_scale(scale, scale_t, invert), opt_iptr(noop), cur_stream());

@@ -40,9 +40,9 @@ void mt_lamb_legacy_stage2_op(at::Tensor noop, const TensorLists& lists, at::Ten
                               at::Tensor update_norms, double lr, double weight_decay,
                               bool use_nvlamb);
 void mt_novograd_op(at::Tensor noop, const TensorLists& lists, at::Tensor v, at::Tensor grad_norms,
-                    bool first_step, double lr, OptT lr_t, double beta1, double beta2, double eps,
-                    int64_t step, OptT step_t, bool bias_correction, double wd,
-                    bool grad_averaging, int64_t mode, int64_t norm_type, double scale,
+                    bool first_step, OptT first_step_flag, double lr, OptT lr_t, double beta1,
+                    double beta2, double eps, int64_t step, OptT step_t, bool bias_correction,
+                    double wd, bool grad_averaging, int64_t mode, int64_t norm_type, double scale,
                     OptT scale_t, bool scale_inv);
 void mt_adagrad_op(at::Tensor noop, const TensorLists& lists, double lr, OptT lr_t, double eps,
                    int64_t mode, double wd, double scale, OptT scale_t, bool scale_inv);

@@ -25,6 +25,15 @@ inline DType dtype_of(const at::Tensor& t) {
   return DType::F32;
 }
 
+// The gfx950 multi-tensor kernels are instantiated for fp32 / fp16 / bf16 only
+// (dispatch1 in mt_device.h launches nothing for any other type): a GPU tensor of
+// another dtype is an error, never a silent no-op.  The CPU path converts through fp32.
+inline void check_kernel_dtype(const at::Tensor& t, const char* what) {
+  const at::ScalarType s = t.scalar_type();
+  TORCH_CHECK(s == at::kFloat || s == at::kHalf || s == at::kBFloat16, what,
+              ": the GPU kernels take float32 / float16 / bfloat16 tensors, got ", s);
+}
+
 inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
 // A scale factor from Python: value, optional device scalar, optional reciprocal.
@@ -66,7 +75,8 @@ struct MTPlan {
 MTPlan mt_plan(const TensorLists& lists);
 
 // Shared validation: every list has the same length, matching numel per slot,
-// contiguous tensors.  Returns true if the lists live on the GPU.
+// contiguous tensors; on the GPU, a dtype the kernels are instantiated for
+// (check_kernel_dtype).  Returns true if the lists live on the GPU.
 bool mt_validate(const TensorLists& lists, int min_depth, int max_depth);
 
 }  // namespace amd

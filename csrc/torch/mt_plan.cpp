@@ -93,6 +93,7 @@ bool mt_validate(const TensorLists& lists, int min_depth, int max_depth) {
       } else {
         TORCH_CHECK(t.is_cuda() == on_gpu, "all tensors must be on the same device type");
       }
+      if (on_gpu) check_kernel_dtype(t, "multi_tensor ops");
     }
   }
   return on_gpu;
