@@ -35,13 +35,24 @@ def sdpa_masks(key_padding_mask, attn_mask, mask_additive, B, Tq, Tk, dtype, dev
 def attention_bshd(q, k, v, dropout_p, key_padding_mask=None, attn_mask=None,
                    mask_additive=False, allow_fused=True):
     """q [B, Tq, H, D], k/v [B, Tk, H, D] (any strides) -> [B, Tq, H, D].
-    gfx950 fused kernels when eligible (no masks, Tq == Tk, D == 64, 16-bit),
-    PyTorch SDPA otherwise."""
+    gfx950 fused kernels when eligible (no attn_mask, Tq == Tk, D == 64, 16-bit; a
+    key-padding mask - boolean / byte, or additive under ``mask_additive``, or an
+    ops.attention.PreparedKeyMask - is applied inside the kernels), PyTorch SDPA
+    otherwise."""
     B, Tq, H, D = q.shape
     Tk = k.size(1)
-    if (allow_fused and key_padding_mask is None and attn_mask is None and Tq == Tk
-            and fused_attn.supported(q, D)):
-        return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p)
+    if allow_fused and attn_mask is None and Tq == Tk and fused_attn.supported(q, D):
+        if key_padding_mask is None:
+            return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p)
+        if isinstance(key_padding_mask, fused_attn.PreparedKeyMask):
+            return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p,
+                                              key_bias=key_padding_mask)
+        kp = key_padding_mask.to(q.device)
+        if mask_additive:
+            return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p,
+                                              key_bias=kp.float())
+        return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p,
+                                          key_padding_mask=kp.bool())
     mask = sdpa_masks(key_padding_mask, attn_mask, mask_additive, B, Tq, Tk, q.dtype, q.device)
     o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
                                        attn_mask=mask, dropout_p=dropout_p,

@@ -1,7 +1,7 @@
 """BERT (Devlin et al. 2018) for pre-training, defined in-repo (no transformers
 download): post-LN encoder with FusedLayerNorm, fused QKV projection, the gfx950 fused
-attention kernels (ops/attention.py; PyTorch SDPA when a padding mask is given
-or off-GPU), masked-LM head on the
+attention kernels (ops/attention.py, with the padding mask applied inside them;
+PyTorch SDPA off-GPU, in fp32 or with fused_attention=False), masked-LM head on the
 gathered masked positions only (NVIDIA's pretraining recipe, max_predictions
 per sequence) with the decoder tied to the word embeddings, and the NSP head.
 
@@ -85,10 +85,12 @@ class BertSelfAttention(nn.Module):
     def _lin(self, m, x):
         return fused_dense_function(x, m.weight, m.bias) if self.fused_dense else m(x)
 
-    def forward(self, x, attn_mask=None):
+    def forward(self, x, attn_mask=None, key_mask=None):
         """Returns (attention output, x as the residual branch).  With fused_dense the
         residual is the QKV layer's skip output, so the input gradient of the block
-        is one accumulating GEMM (no separate residual-gradient add)."""
+        is one accumulating GEMM (no separate residual-gradient add).  attn_mask: additive
+        [b, 1, 1, s] for the SDPA path; key_mask: the same padding mask prepared for the
+        fused kernels (ops.attention.PreparedKeyMask), which then take it instead."""
         b, s, hd = x.shape
         if self.fused_dense:
             qkv, skip = fused_dense_skip_function(x, self.qkv.weight, self.qkv.bias)
@@ -96,9 +98,12 @@ class BertSelfAttention(nn.Module):
             qkv, skip = self.qkv(x), x
         qkv = qkv.view(b, s, 3, self.h, self.d)
         p = self.p if self.training else 0.0
-        if self.fused and attn_mask is None and fused_attn.supported(qkv, self.d):
-            o = fused_attn.fused_attention_qkv(qkv, causal=False, dropout_p=p)
+        if (self.fused and (attn_mask is None or key_mask is not None)
+                and fused_attn.supported(qkv, self.d)):
+            o = fused_attn.fused_attention_qkv(qkv, causal=False, dropout_p=p, key_bias=key_mask)
             return self._lin(self.dense, o.view(b, s, hd)), skip
+        if attn_mask is None and key_mask is not None:
+            raise ValueError("key_mask is for the fused attention path; pass attn_mask too")
         qkv = qkv.permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
         o = F.scaled_dot_product_attention(q, k, v, attn_mask=attn_mask, dropout_p=p)
@@ -119,8 +124,8 @@ class BertLayer(nn.Module):
         self.fused_dense = cfg.fused_dense
         self.approximate = {"gelu_tanh": "tanh", "gelu": "none"}[cfg.hidden_act]
 
-    def forward(self, x, attn_mask=None):
-        a, x = self.attention(x, attn_mask)
+    def forward(self, x, attn_mask=None, key_mask=None):
+        a, x = self.attention(x, attn_mask, key_mask)
         x, _ = fused_add_dropout_layer_norm(x, a, self.attn_ln, self.attn_dropout.p,
                                             self.training)
         if self.fused_dense:
@@ -134,6 +139,12 @@ class BertLayer(nn.Module):
                                             self.training)[0]
 
 
+def additive_attention_mask(attention_mask, dtype):
+    """BERT's [b, s] attention_mask (1 = attend, 0 = padding) as an additive key bias:
+    0 on kept keys, -10000 on padded ones."""
+    return (1.0 - attention_mask.to(dtype)) * -10000.0
+
+
 class BertModel(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -144,12 +155,20 @@ class BertModel(nn.Module):
 
     def forward(self, input_ids, token_type_ids, attention_mask=None):
         x = self.embeddings(input_ids, token_type_ids)
-        mask = None
+        mask = key_mask = None
         if attention_mask is not None:
             # [b, s] 1 = keep -> additive [b, 1, 1, s]
-            mask = (1.0 - attention_mask[:, None, None, :].to(x.dtype)) * -10000.0
+            mask = additive_attention_mask(attention_mask, x.dtype)[:, None, None, :]
+            head_dim = self.config.hidden_size // self.config.num_attention_heads
+            if (self.config.fused_attention and x.is_cuda and head_dim == 64
+                    and _native.available()):
+                # the same -10000 bias (never -inf: no row is fully masked), prepared once
+                # for the fused kernels of all layers (each layer takes them when its qkv
+                # is 16-bit, the SDPA path with `mask` otherwise)
+                key_mask = fused_attn.prepare_key_mask(
+                    additive_attention_mask(attention_mask, torch.float32))
         for layer in self.layers:
-            x = layer(x, mask)
+            x = layer(x, mask, key_mask)
         pooled = torch.tanh(self.pooler(x[:, 0]))
         return x, pooled
 

@@ -12,9 +12,19 @@ free); its backward writes dQ/dK/dV straight into ONE packed buffer, so the
 projection's input gradient needs no concatenation.  Layout-generic views
 ([S, B, ...] sequence-first included) work: the kernels take strides.
 
+Key masks: ``key_padding_mask`` ([B, S] bool, True = masked key, Apex's convention)
+or ``key_bias`` ([B, S] float, added to the scaled scores, ``-inf`` allowed) mask keys
+per batch element inside the kernels.  ``prepare_key_mask`` turns either into the
+form the kernels read (an fp32 bias row in log2 units plus one liveness byte per
+64-key tile) in one launch without a host sync; pass the returned ``PreparedKeyMask``
+in place of the mask to share it between the layers of a model.  64-key tiles whose
+keys are all masked are skipped (no loads, no math) wherever they lie, masked keys
+get exactly zero dK / dV, and a query whose keys are all masked gets o = 0 and
+dq = 0 (its lse is unspecified) instead of NaN.
+
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64, q/k/v of one
-sequence length, no additive mask.  Callers fall back to
-``F.scaled_dot_product_attention`` otherwise.
+sequence length, no mask other than a per-batch key mask (a [Tq, Tk] ``attn_mask``
+is not fused).  Callers fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
 from __future__ import annotations
 
@@ -66,25 +76,81 @@ def _seed(dropout_p: float) -> int:
     return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
 
 
+class PreparedKeyMask:
+    """A [B, S] key mask in the form the kernels read (``prepare_key_mask``):
+    ``bias`` fp32 [B, round_up(S, 64)] in log2 units (-inf = masked, -inf past S) and
+    ``live`` uint8 [B, round_up(S, 64) / 64] (0 = every key of the 64-key tile masked)."""
+
+    __slots__ = ("bias", "live", "B", "S")
+
+    def __init__(self, bias, live, B, S):
+        self.bias, self.live, self.B, self.S = bias, live, B, S
+
+
+def prepare_key_mask(mask: torch.Tensor) -> PreparedKeyMask:
+    """mask [B, S] on the GPU: bool / uint8 (True / non-zero = masked key) or floating
+    (additive, added to the scaled scores; -inf masks).  One kernel launch, no host sync
+    (graph-capture safe).  The result serves every fused attention call with the same
+    (B, S), forward and backward."""
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 2:
+        raise ValueError("key mask must be a [B, S] tensor, got %s" % (
+            tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__))
+    if not mask.is_cuda:
+        raise ValueError("key mask must be on the GPU, got a %s tensor" % mask.device)
+    B, S = mask.shape
+    bias, live = _C().prepare_key_mask(mask.detach().contiguous(), S)
+    return PreparedKeyMask(bias, live, B, S)
+
+
+def _key_mask(key_padding_mask, key_bias, like):
+    """The (bias, live) pair of a call's mask arguments for q ``like`` [B, S, H, 64], or
+    (None, None)."""
+    if key_padding_mask is None and key_bias is None:
+        return None, None
+    if key_padding_mask is not None and key_bias is not None:
+        raise ValueError("give key_padding_mask (boolean) or key_bias (additive), not both")
+    B, S = like.size(0), like.size(1)
+    m = key_padding_mask if key_bias is None else key_bias
+    if not isinstance(m, PreparedKeyMask):
+        if key_bias is None and m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("key_padding_mask must be bool (True = masked key), got %s; an "
+                             "additive mask goes to key_bias" % m.dtype)
+        if key_bias is not None and not m.is_floating_point():
+            raise ValueError("key_bias must be a floating additive mask, got %s" % m.dtype)
+        if tuple(m.shape) != (B, S):
+            raise ValueError("key mask must be [B, S] = [%d, %d], got %s" % (B, S, tuple(m.shape)))
+        if m.device != like.device:
+            raise ValueError("key mask is on %s, q on %s" % (m.device, like.device))
+        m = prepare_key_mask(m)
+    if (m.B, m.S) != (B, S):
+        raise ValueError("prepared key mask is for [B, S] = [%d, %d], q has [%d, %d]" % (
+            m.B, m.S, B, S))
+    if m.bias.device != like.device:
+        raise ValueError("key mask is on %s, q on %s" % (m.bias.device, like.device))
+    return m.bias, m.live
+
+
 class FusedAttentionFunction(torch.autograd.Function):
-    """o = softmax(q k^T * scale [+ causal mask]) [dropout] v on [B, S, H, 64] views."""
+    """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v on
+    [B, S, H, 64] views; (kbias, klive) is a prepared key mask or (None, None)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, dropout_p, scale, seed):
-        o, lse = _C().fwd(q, k, v, bool(causal), float(dropout_p), int(seed), float(scale))
-        ctx.save_for_backward(q, k, v, o, lse)
+    def forward(ctx, q, k, v, causal, dropout_p, scale, seed, kbias=None, klive=None):
+        o, lse = _C().fwd(q, k, v, bool(causal), float(dropout_p), int(seed), float(scale),
+                          kbias, klive)
+        ctx.save_for_backward(q, k, v, o, lse, kbias, klive)
         ctx.cfg = (bool(causal), float(dropout_p), int(seed), float(scale))
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        q, k, v, o, lse, kbias, klive = ctx.saved_tensors
         causal, p, seed, scale = ctx.cfg
         dq = torch.empty_like(q, memory_format=torch.contiguous_format)
         dk = torch.empty_like(k, memory_format=torch.contiguous_format)
         dv = torch.empty_like(v, memory_format=torch.contiguous_format)
-        _C().bwd(do, q, k, v, o, lse, causal, p, seed, scale, dq, dk, dv)
-        return dq, dk, dv, None, None, None, None
+        _C().bwd(do, q, k, v, o, lse, causal, p, seed, scale, dq, dk, dv, kbias, klive)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 class FusedQKVAttentionFunction(torch.autograd.Function):
@@ -92,31 +158,40 @@ class FusedQKVAttentionFunction(torch.autograd.Function):
     backward returns one packed dqkv of qkv's layout."""
 
     @staticmethod
-    def forward(ctx, qkv, causal, dropout_p, scale, seed):
+    def forward(ctx, qkv, causal, dropout_p, scale, seed, kbias=None, klive=None):
         q, k, v = qkv.unbind(2)
-        o, lse = _C().fwd(q, k, v, bool(causal), float(dropout_p), int(seed), float(scale))
-        ctx.save_for_backward(qkv, o, lse)
+        o, lse = _C().fwd(q, k, v, bool(causal), float(dropout_p), int(seed), float(scale),
+                          kbias, klive)
+        ctx.save_for_backward(qkv, o, lse, kbias, klive)
         ctx.cfg = (bool(causal), float(dropout_p), int(seed), float(scale))
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse = ctx.saved_tensors
+        qkv, o, lse, kbias, klive = ctx.saved_tensors
         causal, p, seed, scale = ctx.cfg
         dqkv = torch.empty_like(qkv)
         q, k, v = qkv.unbind(2)
         dq, dk, dv = dqkv.unbind(2)
-        _C().bwd(do, q, k, v, o, lse, causal, p, seed, scale, dq, dk, dv)
-        return dqkv, None, None, None, None
+        _C().bwd(do, q, k, v, o, lse, causal, p, seed, scale, dq, dk, dv, kbias, klive)
+        return dqkv, None, None, None, None, None, None
 
 
-def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None):
-    """q, k, v: [B, S, H, 64] -> o [B, S, H, 64]."""
+def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
+                    key_bias=None):
+    """q, k, v: [B, S, H, 64] -> o [B, S, H, 64].  key_padding_mask: [B, S] bool, True =
+    masked key; key_bias: [B, S] float, added to the scaled scores; either may be a
+    ``PreparedKeyMask``."""
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
-    return FusedAttentionFunction.apply(q, k, v, causal, dropout_p, scale, _seed(dropout_p))
+    kbias, klive = _key_mask(key_padding_mask, key_bias, q)
+    return FusedAttentionFunction.apply(q, k, v, causal, dropout_p, scale, _seed(dropout_p),
+                                        kbias, klive)
 
 
-def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None):
-    """qkv: [B, S, 3, H, 64] -> o [B, S, H, 64]."""
+def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
+                        key_bias=None):
+    """qkv: [B, S, 3, H, 64] -> o [B, S, H, 64]; masks as in ``fused_attention``."""
     scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
-    return FusedQKVAttentionFunction.apply(qkv, causal, dropout_p, scale, _seed(dropout_p))
+    kbias, klive = _key_mask(key_padding_mask, key_bias, qkv)
+    return FusedQKVAttentionFunction.apply(qkv, causal, dropout_p, scale, _seed(dropout_p),
+                                           kbias, klive)

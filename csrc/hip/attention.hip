@@ -27,6 +27,16 @@
 // loops over queries, "unswapped" S = Q.K^T so dV = P^T.dO and dK = dS^T.Q sum
 // over the register rows) - no atomics (bitwise reproducible), no LDS transposes
 // of score tiles, no preprocess launch.
+//
+// Key masks (KMASK kernels): a per-batch [B, S] key mask (boolean or additive) is
+// prepared ONCE per forward by attn_kmask_prep_k into an fp32 bias [B, Sp] in log2
+// units (-inf = masked, columns >= S are -inf) plus one liveness byte per (b, 64-key
+// tile); every layer's forward and backward reuse the pair.  Scores become
+// x * scale_log2 + bias[b][key]; forward and dQ skip dead tiles (no DMA, no compute)
+// by walking the set bits of a ballot of the liveness bytes, the tile's 64 bias floats
+// ride the K/V DMA ring; a dK/dV workgroup loads its lanes' biases once and writes
+// zeros when its 128 keys are all dead.  The KMASK=false instantiations are the
+// mask-free kernels unchanged.
 #include <cstdlib>
 
 #include "amd_dev.h"
@@ -225,6 +235,55 @@ struct AttnArgs {
   uint32_t thr8;     // dropout threshold round(p * 256) on a hash byte, 0 = no dropout
   float inv_keep;    // 1 / (1 - p)
   uint32_t seed;
+  const float* kbias;          // KMASK: [B][lse_stride] log2-unit key bias
+  const unsigned char* klive;  // KMASK: [B][lse_stride / 64] tile liveness
+};
+
+// ------------------------------------------------------------------- key-mask prepare
+// One thread per key of a 64-key tile: bias = -inf / 0 (boolean mask, non-zero =
+// masked) or mask * log2(e) (additive), -inf past S; the tile's liveness byte is
+// "some key has a bias above -inf".
+template <typename M, bool BOOLEAN>
+__global__ void __launch_bounds__(64) attn_kmask_prep_k(const M* __restrict__ mask,
+                                                        float* __restrict__ bias,
+                                                        unsigned char* __restrict__ live, int S,
+                                                        int Sp) {
+  const int nt = Sp / kAKT;
+  const int b = blockIdx.x / nt, t = blockIdx.x - b * nt;
+  const int key = t * kAKT + (int)threadIdx.x;
+  float v = -INFINITY;
+  if (key < S) {
+    const M mv = mask[(int64_t)b * S + key];
+    if constexpr (BOOLEAN) v = mv != 0 ? -INFINITY : 0.f;
+    else v = (float)mv * 1.4426950408889634f;
+  }
+  bias[(int64_t)b * Sp + key] = v;
+  const bool any = __any(!(v == -INFINITY));
+  if (threadIdx.x == 0) live[(int64_t)b * nt + t] = any ? 1 : 0;
+}
+
+// The live key tiles of one batch element, in order: ballots 64 liveness bytes at a time
+// (the only plain global load, once per 4096 keys, taken right before the ring's own
+// vmcnt(0) so it drains nothing) and steps through the set bits, so dead tiles cost
+// neither DMA nor compute wherever they lie (padding on either side, holes).
+struct LiveTiles {
+  const unsigned char* live;
+  int nkt, lane, c0;
+  unsigned long long lm;
+  __device__ __forceinline__ LiveTiles(const unsigned char* live_, int nkt_, int lane_)
+      : live(live_), nkt(nkt_), lane(lane_), c0(-64), lm(0) {}
+  // the next live tile; nkt when none is left
+  __device__ __forceinline__ int next() {
+    while (lm == 0) {
+      c0 += 64;
+      if (c0 >= nkt) return nkt;
+      const int t = c0 + lane;
+      lm = __ballot(t < nkt && live[t] != 0);
+    }
+    const int kt = c0 + __builtin_ctzll(lm);
+    lm &= lm - 1;
+    return kt;
+  }
 };
 
 // ---------------------------------------------------------------------------- forward
@@ -251,10 +310,12 @@ __device__ __forceinline__ float max_halves(float x) {
   return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
 }
 
-template <typename T, bool CAUSAL, bool DROP>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   typedef typename Frag<T>::v8 v8;
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * 2 * kAKT * kARow];  // 2 x (K, V)
+  constexpr int KV = 2 * kAKT * kARow;          // K and V images of one tile
+  constexpr int BUF = KV + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];  // 2 x (K, V[, bias])
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform to the compiler
   const int hl = lane >> 5, c32 = lane & 31;
@@ -294,9 +355,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
     kof[i] = row_off<T>(row, a.kss, (swz_rows(row, pch) - row * kARow) >> 4);  // logical chunk at pch
     vof[i] = row_off<T>(row, a.vss, (swz_tr(row, pch) - row * kARow) >> 4);
   }
+  const float* kbias = KMASK ? a.kbias + (int64_t)b * a.lse_stride : nullptr;
   auto issue = [&](int kt, int buf) {
-    unsigned char* Kl = lds + buf * 2 * kAKT * kARow;
+    unsigned char* Kl = lds + buf * BUF;
     unsigned char* Vl = Kl + kAKT * kARow;
+    if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
+      if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, Kl + KV);
+    }
     if ((kt + 1) * kAKT <= a.S) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
       const T* vb = tile_base(V, kt * kAKT, a.vss);
@@ -343,11 +408,15 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
         vhi[dt][t][s] = tr_addr(r0 + 8, c0, lane);
       }
 
-  auto step = [&](int kt, int buf) {
+  auto step = [&](int kt, int buf, int nx) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (kt + 1 < nkt) issue(kt + 1, buf ^ 1);
-    const unsigned char* Kl = lds + buf * 2 * kAKT * kARow;
+    if constexpr (KMASK) {
+      if (nx < nkt) issue(nx, buf ^ 1);
+    } else {
+      if (kt + 1 < nkt) issue(kt + 1, buf ^ 1);
+    }
+    const unsigned char* Kl = lds + buf * BUF;
     const unsigned char* Vl = Kl + kAKT * kARow;
     const int k0 = kt * kAKT;
     if (CAUSAL && k0 > qb0 + wid * 32 + 31) return;  // whole tile masked for this wave
@@ -360,41 +429,88 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
 #pragma unroll
       for (int s = 0; s < 4; ++s) x[t] = mfma32<T>(lds_row8<T>(Kl, koff[t][s]), qf[s], x[t]);
     }
-    // mask (boundary / diagonal tiles only: the test is wave-uniform), running
-    // max on the raw scores, then one fma + exp2 per score in log2 units
-    const bool need_mask =
-        (k0 + kAKT > a.S) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
-    if (need_mask) {
+    bool grow;
+    float alpha, psum = 0.f;
+    if constexpr (KMASK) {
+      // biased scores in log2 units first (the bias is -inf on masked keys and past S),
+      // then the running max over the BIASED values.  A query with no live key so far
+      // keeps m = -inf: its exponent offset is 0 instead, so p = exp2(-inf) = 0, never
+      // exp2(-inf - -inf).
+      const float* bl = reinterpret_cast<const float*>(Kl + KV);
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          const float4 bv = *reinterpret_cast<const float4*>(bl + 32 * t + 8 * rq + 4 * hl);
+          const float be[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            x[t][4 * rq + e] = fmaf(x[t][4 * rq + e], a.scale_log2, be[e]);
+        }
+      if (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
+            if (key > q) x[t][r] = -INFINITY;
+          }
+      }
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, x[t][r]);
+      tmax = max_halves(tmax);
+      const float mnew = fmaxf(m, tmax);
+      const float msafe = mnew == -INFINITY ? 0.f : mnew;
+      grow = __any(mnew != m);
+      alpha = grow ? fexp2(m - msafe) : 1.f;
+      m = mnew;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
-          if (key >= a.S || (CAUSAL && key > q)) x[t][r] = -INFINITY;
+          const float p = fexp2(x[t][r] - msafe);
+          psum += p;
+          x[t][r] = p;
+        }
+    } else {
+      // mask (boundary / diagonal tiles only: the test is wave-uniform), running
+      // max on the raw scores, then one fma + exp2 per score in log2 units
+      const bool need_mask =
+          (k0 + kAKT > a.S) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+      if (need_mask) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
+            if (key >= a.S || (CAUSAL && key > q)) x[t][r] = -INFINITY;
+          }
+      }
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, x[t][r]);
+      tmax = max_halves(tmax);
+      const float mnew = fmaxf(m, tmax * a.scale_log2);
+      // the O / l rescale by exp2(m - mnew) is skipped while no query of the wave
+      // raised its running max (alpha == 1 exactly: same math, 32 fewer multiplies
+      // per tile - the common case once the first tiles have set the max)
+      grow = __any(mnew != m);
+      alpha = grow ? fexp2(m - mnew) : 1.f;
+      m = mnew;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = fexp2(fmaf(x[t][r], a.scale_log2, -mnew));
+          psum += p;
+          x[t][r] = p;
         }
     }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, x[t][r]);
-    tmax = max_halves(tmax);
-    const float mnew = fmaxf(m, tmax * a.scale_log2);
-    // the O / l rescale by exp2(m - mnew) is skipped while no query of the wave
-    // raised its running max (alpha == 1 exactly: same math, 32 fewer multiplies
-    // per tile - the common case once the first tiles have set the max)
-    const bool grow = __any(mnew != m);
-    const float alpha = grow ? fexp2(m - mnew) : 1.f;
-    m = mnew;
-    float psum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = fexp2(fmaf(x[t][r], a.scale_log2, -mnew));
-        psum += p;
-        x[t][r] = p;
-      }
     l = l * alpha + psum;
     if (grow) {
 #pragma unroll
@@ -427,8 +543,19 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
           o[dt] = mfma32<T>(lds_tr8<T>(Vl, vlo[dt][t][s], vhi[dt][t][s]), pf, o[dt]);
       }
   };
-  issue(0, 0);
-  for (int kt = 0; kt < nkt; ++kt) step(kt, kt & 1);
+  if constexpr (KMASK) {
+    LiveTiles lt(a.klive + (int64_t)b * (a.lse_stride / kAKT), nkt, lane);
+    int kt = lt.next();
+    if (kt < nkt) issue(kt, 0);
+    for (int slot = 0; kt < nkt; slot ^= 1) {
+      const int nx = lt.next();
+      step(kt, slot, nx);
+      kt = nx;
+    }
+  } else {
+    issue(0, 0);
+    for (int kt = 0; kt < nkt; ++kt) step(kt, kt & 1, 0);
+  }
 
   const float lt = l + __shfl_xor(l, 32);
   const float inv = lt > 0.f ? (DROP ? a.inv_keep : 1.f) / lt : 0.f;
@@ -451,13 +578,20 @@ struct AttnBwdArgs {
   void* dv;
   int64_t dqsb, dqss, dqsh, dksb, dkss, dksh, dvsb, dvss, dvsh;
   const float* lse;  // [B][H][lse_stride] log2 units
-  float* D;          // [B][H][lse_stride] rowsum(dO * O)
+  float* D;          // [B][H][lse_stride] rowsum(dO * O); KMASK: [2][B][H][lse_stride]
   int B, H, S, lse_stride;
   float scale, scale_log2;
   uint32_t thr8;
   float inv_keep;
   uint32_t seed;
+  const float* kbias;          // KMASK: [B][lse_stride] log2-unit key bias
+  const unsigned char* klive;  // KMASK: [B][lse_stride / 64] tile liveness
 };
+
+// A query none of whose keys is live has lse = -inf (or whatever the caller stored);
+// read as +inf it makes every recomputed p = exp2(score - lse) exactly 0, where -inf
+// would give exp2(-inf - -inf).
+__device__ __forceinline__ float lse_guard(float lse) { return lse == -INFINITY ? INFINITY : lse; }
 
 // dK / dV: a workgroup owns 128 keys (32 per wave, one per lane column), loops
 // over 64-query tiles.  Scores are computed unswapped, S[q][key] = Q . K^T with
@@ -467,8 +601,10 @@ struct AttnBwdArgs {
 // and dO tiles sit in LDS twice: a row image (A operand of S and dP) and a
 // transposed-read image (A operand of dV^T / dK^T); the tile's lse / D values
 // ride the same DMA ring (no plain global loads inside the loop, which would
-// make the compiler's vmcnt waits drain the prefetch).
-template <typename T, bool CAUSAL, bool DROP>
+// make the compiler's vmcnt waits drain the prefetch).  KMASK: a lane's key bias is
+// loop-invariant (one load); a workgroup whose 128 keys are all dead writes zeros and
+// leaves, a wave whose 32 keys are all dead keeps the ring's barriers and skips the math.
+template <typename T, bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;     // 8 KiB
@@ -484,13 +620,36 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   const int kw0 = kb0 + wid * 32;
   const int key = kw0 + c32;
   const int kk = key < a.S ? key : a.S - 1;
+  float kbias = 0.f;
+  bool wave_dead = false;
+  if constexpr (KMASK) {
+    const int nlt = a.lse_stride / kAKT;
+    const unsigned char* lv = a.klive + (int64_t)b * nlt;
+    const int t0 = kb0 / kAKT;
+    if (lv[t0] == 0 && (t0 + 1 >= nlt || lv[t0 + 1] == 0)) {
+      if (key < a.S) {
+        T* dvp = static_cast<T*>(a.dv) + b * a.dvsb + (int64_t)key * a.dvss + hh * a.dvsh;
+        T* dkp = static_cast<T*>(a.dk) + b * a.dksb + (int64_t)key * a.dkss + hh * a.dksh;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          *reinterpret_cast<uint4*>(dvp + 32 * hl + 8 * i) = uint4{0u, 0u, 0u, 0u};
+          *reinterpret_cast<uint4*>(dkp + 32 * hl + 8 * i) = uint4{0u, 0u, 0u, 0u};
+        }
+      }
+      return;
+    }
+    kbias = key < a.S ? a.kbias[(int64_t)b * a.lse_stride + key] : -INFINITY;
+    wave_dead = !__any(kbias > -INFINITY);
+  }
   // dropout lattice point of (query key & 3, this lane's key quad)
   const uint32_t kdrop = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)(key >> 2) * kDropK +
                                     (uint32_t)(key & 3) * kDropQ
                               : 0u;
   const T* Q = static_cast<const T*>(a.q) + b * a.qsb + hh * a.qsh;
   const T* dO = static_cast<const T*>(a.dout) + b * a.dsb + hh * a.dsh;
-  const float* lse = a.lse + (int64_t)bh * a.lse_stride;
+  // KMASK: the guarded copy of lse that the dQ kernel left behind D
+  const float* lse = (KMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
+                     (int64_t)bh * a.lse_stride;
   const float* Dr = a.D + (int64_t)bh * a.lse_stride;
 
   // K^T / V^T fragments (B operands): key = this lane's column, d = 16s + 8hl + j
@@ -569,6 +728,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     const float* st_lse = reinterpret_cast<const float*>(base + 4 * IMG);
     const float* st_D = st_lse + 64;
     const int q0 = qt * kAKT;
+    if (KMASK && wave_dead) continue;  // wave-uniform: dk = dv = 0 for all 32 keys
     // the four stages of one 32-query half h (S / dP products, softmax backward,
     // mask, dV / dK products)
     auto sdp = [&](int h, f32x16_t& sc, f32x16_t& dp) {
@@ -606,7 +766,9 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
           const int r = 4 * g + e;
           bool keep = true;
           if (DROP) keep = drop_keep8(hq[e], key & 3, a.thr8);
-          float p = fexp2(fmaf(sc[r], a.scale_log2, -lsev[e]));
+          float p;
+          if constexpr (KMASK) p = fexp2(fmaf(sc[r], a.scale_log2, kbias - lsev[e]));
+          else p = fexp2(fmaf(sc[r], a.scale_log2, -lsev[e]));
           // dropped dP scaled by 1/(1-p); the dropped P feeding dV^T is left unscaled
           // (the factor is applied to dV once, at the store)
           const float dpz = DROP ? (keep ? dp[r] * a.inv_keep : 0.f) : dp[r];
@@ -637,9 +799,12 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     // wave-uniform: no (query, key) of the whole 64 x 32 tile needs a mask - the
     // common case runs both halves as ONE straight-line block, so the compiler can
     // put half 1's S / dP MFMAs beside half 0's softmax VALU and half 0's dV / dK
-    // MFMAs beside half 1's (a block split by a mask branch serialises them)
+    // MFMAs beside half 1's (a block split by a mask branch serialises them).
+    // KMASK takes the half-by-half path always: the straight-line block sits at 246-256
+    // VGPRs, and the bias on top of that spilled (1-33 VGPRs, reloaded inside the loop)
+    // in whichever instantiation the register allocator liked least.
     const bool clean = (q0 + kAKT <= a.S) && (!CAUSAL || kw0 + 31 <= q0);
-    if (clean) {
+    if (!KMASK && clean) {
       f32x16_t sc0, dp0, sc1, dp1;
       sdp(0, sc0, dp0);
       sdp(1, sc1, dp1);
@@ -674,12 +839,14 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
 // tiles in the forward's swapped orientation S^T[key][q] = K . Q^T, so a lane's
 // lse / D are scalars and dQ^T = K^T . dS^T consumes dS^T from the accumulator.
 // K sits in LDS as a row image (A of S^T) and a transposed image (A of dQ^T);
-// V as a row image (A of dP^T = V . dO^T).
-template <typename T, bool CAUSAL, bool DROP>
+// V as a row image (A of dP^T = V . dO^T).  KMASK: the tile's bias rides the ring and
+// dead tiles are skipped as in the forward.
+template <typename T, bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * 3 * IMG];
+  constexpr int BUF = 3 * IMG + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform to the compiler
   const int hl = lane >> 5, c32 = lane & 31;
@@ -705,7 +872,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       of[s] = *reinterpret_cast<const v8*>(Op + 16 * s + 8 * hl);
     }
   }
-  const float lse_q = a.lse[(int64_t)bh * a.lse_stride + qq];
+  const float lse_q = KMASK ? lse_guard(a.lse[(int64_t)bh * a.lse_stride + qq])
+                            : a.lse[(int64_t)bh * a.lse_stride + qq];
   // D = rowsum(dO * O) of this lane's query, from the dO fragments already in
   // registers (the two 32-lane halves hold complementary d ranges); written for the
   // dK / dV kernel, which runs after this one (no separate preprocess launch)
@@ -720,7 +888,12 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       for (int j = 0; j < 8; ++j) part = fmaf((float)of[s][j], (float)ov[j], part);
     }
     D_q = part + __shfl_xor(part, 32);
-    if (hl == 0 && q < a.S) a.D[(int64_t)bh * a.lse_stride + q] = D_q;
+    if constexpr (KMASK) {  // D itself: refined at the end; here the guarded lse, so the
+                            // dK/dV kernel need not guard per score
+      if (hl == 0 && q < a.S) a.D[((int64_t)a.B * a.H + bh) * a.lse_stride + q] = lse_q;
+    } else {
+      if (hl == 0 && q < a.S) a.D[(int64_t)bh * a.lse_stride + q] = D_q;
+    }
   }
 
   int nkt = (a.S + kAKT - 1) / kAKT;
@@ -738,9 +911,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     kto[i] = row_off<T>(row, a.kss, (swz_tr(row, pch) - row * kARow) >> 4);
     vro[i] = row_off<T>(row, a.vss, chr);
   }
-  // images per buffer: 0 = K rows, 1 = K transposed, 2 = V rows
+  // images per buffer: 0 = K rows, 1 = K transposed, 2 = V rows[, 3 = bias]
+  const float* kbias = KMASK ? a.kbias + (int64_t)b * a.lse_stride : nullptr;
   auto issue = [&](int kt, int buf) {
-    unsigned char* base = lds + buf * 3 * IMG;
+    unsigned char* base = lds + buf * BUF;
+    if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
+      if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, base + 3 * IMG);
+    }
     if ((kt + 1) * kAKT <= a.S) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
       const T* vb = tile_base(V, kt * kAKT, a.vss);
@@ -771,6 +948,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   f32x16_t dq[2];
 #pragma unroll
   for (int i = 0; i < 16; ++i) dq[0][i] = dq[1][i] = 0.f;
+  // KMASK: sum over keys of this lane's dS = p (dP~ - D_q).  The p of a row sum to 1, so
+  // the exact dS sum to 0 and what is left is (exact D) - D_q: the rounding of the 16-bit
+  // O inside D_q = rowsum(dO * O).  Where few keys are live and carry all of p (padding
+  // under dropout) that error lands whole on their dK, so the D handed to the dK/dV
+  // kernel is D_q plus this sum (one add per score); dQ itself keeps D_q, its own error
+  // from it is spread over the row.
+  [[maybe_unused]] float dsum = 0.f;
   int koff[2][4];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -789,12 +973,26 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
         thi[dt][t][s] = tr_addr(r0 + 8, c0, lane);
       }
 
-  issue(0, 0);
-  for (int kt = 0; kt < nkt; ++kt) {
+  // KMASK: kt walks the live tiles only (nx = the one after kt), the ring slot alternates
+  LiveTiles lt(KMASK ? a.klive + (int64_t)b * (a.lse_stride / kAKT) : nullptr, nkt, lane);
+  int nx = 0, slot = 0;
+  if constexpr (KMASK) {
+    nx = lt.next();
+    if (nx < nkt) issue(nx, 0);
+  } else {
+    issue(0, 0);
+  }
+  for (int kt = KMASK ? nx : 0; kt < nkt; kt = KMASK ? nx : kt + 1) {
+    if constexpr (KMASK) nx = lt.next();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);
-    const unsigned char* base = lds + (kt & 1) * 3 * IMG;
+    if constexpr (KMASK) {
+      if (nx < nkt) issue(nx, slot ^ 1);
+    } else {
+      if (kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);
+    }
+    const unsigned char* base = lds + (KMASK ? slot : (kt & 1)) * BUF;
+    if constexpr (KMASK) slot ^= 1;
     const unsigned char* Kr = base;
     const unsigned char* Kt = base + IMG;
     const unsigned char* Vr = base + 2 * IMG;
@@ -817,12 +1015,19 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
         uint32_t hsh = 0;
         // key quad (k0 + 32t + 8rq + 4hl) >> 2: a literal lattice step
         if (DROP) hsh = drop_mix(tb + (uint32_t)(8 * t + 2 * rq) * kDropK);
+        float be[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (KMASK) {
+          const float4 bv = *reinterpret_cast<const float4*>(
+              reinterpret_cast<const float*>(base + 3 * IMG) + 32 * t + 8 * rq + 4 * hl);
+          be[0] = bv.x; be[1] = bv.y; be[2] = bv.z; be[3] = bv.w;
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * rq + e;
           float dpr = dp[r];
           if (DROP) dpr = drop_keep8(hsh, e, a.thr8) ? dpr * a.inv_keep : 0.f;
-          sc[r] = fexp2(fmaf(sc[r], a.scale_log2, -lse_q)) * (dpr - D_q);
+          if constexpr (KMASK) sc[r] = fexp2(fmaf(sc[r], a.scale_log2, be[e] - lse_q)) * (dpr - D_q);
+          else sc[r] = fexp2(fmaf(sc[r], a.scale_log2, -lse_q)) * (dpr - D_q);
         }
       }
     };
@@ -834,6 +1039,10 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       }
     };
     auto accum = [&](int t, const f32x16_t& sc) {
+      if constexpr (KMASK) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dsum += sc[r];
+      }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const v8 sf = acc_frag<T>(sc, s);
@@ -862,6 +1071,10 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       accum(1, sc1);
     }
   }
+  if constexpr (KMASK) {
+    const float dD = dsum + __shfl_xor(dsum, 32);  // the two halves hold 32 keys each per tile
+    if (hl == 0 && q < a.S) a.D[(int64_t)bh * a.lse_stride + q] = D_q + dD;
+  }
   if (q < a.S)
     store_dT<T>(static_cast<T*>(a.dq) + b * a.dqsb + (int64_t)q * a.dqss + hh * a.dqsh, dq, hl,
                 a.scale);
@@ -882,6 +1095,22 @@ static uint32_t drop_thr8(float p) {
 
 int attn_lse_stride(int S) { return (S + kAKT - 1) / kAKT * kAKT; }
 
+void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, float* bias,
+                           unsigned char* live, hipStream_t st) {
+  const int Sp = attn_lse_stride(S);
+  dim3 grid((unsigned)(B * (Sp / kAKT))), block(64);
+#define PREP_LAUNCH(M, BOOLEAN)                                                               \
+  hipLaunchKernelGGL((attn_kmask_prep_k<M, BOOLEAN>), grid, block, 0, st,                     \
+                     static_cast<const M*>(mask), bias, live, S, Sp)
+  switch (kind) {
+    case AttnMaskKind::Bool8: PREP_LAUNCH(unsigned char, true); break;
+    case AttnMaskKind::F32: PREP_LAUNCH(float, false); break;
+    case AttnMaskKind::F16: PREP_LAUNCH(half_t, false); break;
+    case AttnMaskKind::BF16: PREP_LAUNCH(bf16_t, false); break;
+  }
+#undef PREP_LAUNCH
+}
+
 void attn_fwd(const AttnLaunch& L, hipStream_t st) {
   AttnArgs a;
   a.q = L.q; a.k = L.k; a.v = L.v;
@@ -894,15 +1123,18 @@ void attn_fwd(const AttnLaunch& L, hipStream_t st) {
   a.thr8 = drop_thr8(L.dropout);
   a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
   a.seed = L.seed;
+  a.kbias = L.kbias; a.klive = L.klive;
   dim3 grid((L.S + 127) / 128, L.B * L.H), block(kAT);
   const bool drop = a.thr8 != 0;
-#define ATTN_FWD_LAUNCH(T)                                                                                \
-  if (L.causal) {                                                                              \
-    if (drop) hipLaunchKernelGGL((attn_fwd_k<T, true, true>), grid, block, 0, st, a);          \
-    else hipLaunchKernelGGL((attn_fwd_k<T, true, false>), grid, block, 0, st, a);              \
-  } else {                                                                                     \
-    if (drop) hipLaunchKernelGGL((attn_fwd_k<T, false, true>), grid, block, 0, st, a);         \
-    else hipLaunchKernelGGL((attn_fwd_k<T, false, false>), grid, block, 0, st, a);             \
+  const bool kmask = L.kbias != nullptr;
+#define FWD_LAUNCH(T, C, D)                                                                   \
+  if (kmask) hipLaunchKernelGGL((attn_fwd_k<T, C, D, true>), grid, block, 0, st, a);          \
+  else hipLaunchKernelGGL((attn_fwd_k<T, C, D, false>), grid, block, 0, st, a)
+#define ATTN_FWD_LAUNCH(T)                                                                    \
+  if (L.causal) {                                                                             \
+    if (drop) { FWD_LAUNCH(T, true, true); } else { FWD_LAUNCH(T, true, false); }             \
+  } else {                                                                                    \
+    if (drop) { FWD_LAUNCH(T, false, true); } else { FWD_LAUNCH(T, false, false); }           \
   }
   if (L.dtype == DType::BF16) {
     ATTN_FWD_LAUNCH(bf16_t)
@@ -910,6 +1142,7 @@ void attn_fwd(const AttnLaunch& L, hipStream_t st) {
     ATTN_FWD_LAUNCH(half_t)
   }
 #undef ATTN_FWD_LAUNCH
+#undef FWD_LAUNCH
 }
 
 void attn_bwd(const AttnBwdLaunch& L, hipStream_t st) {
@@ -931,26 +1164,24 @@ void attn_bwd(const AttnBwdLaunch& L, hipStream_t st) {
   a.thr8 = drop_thr8(L.dropout);
   a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
   a.seed = L.seed;
+  a.kbias = L.kbias; a.klive = L.klive;
   dim3 grid((L.S + 127) / 128, L.B * L.H), block(kAT);
   const bool drop = a.thr8 != 0;
-#define DQ_LAUNCH(T, C, D) hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D>), grid, block, 0, st, a)
-#define ATTN_BWD_LAUNCH(T)                                                                     \
-  if (L.causal) {                                                                              \
-    if (drop) {                                                                                \
-      DQ_LAUNCH(T, true, true);                                                                \
-      hipLaunchKernelGGL((attn_bwd_dkdv_k<T, true, true>), grid, block, 0, st, a);             \
-    } else {                                                                                   \
-      DQ_LAUNCH(T, true, false);                                                               \
-      hipLaunchKernelGGL((attn_bwd_dkdv_k<T, true, false>), grid, block, 0, st, a);            \
-    }                                                                                          \
-  } else {                                                                                     \
-    if (drop) {                                                                                \
-      DQ_LAUNCH(T, false, true);                                                               \
-      hipLaunchKernelGGL((attn_bwd_dkdv_k<T, false, true>), grid, block, 0, st, a);            \
-    } else {                                                                                   \
-      DQ_LAUNCH(T, false, false);                                                              \
-      hipLaunchKernelGGL((attn_bwd_dkdv_k<T, false, false>), grid, block, 0, st, a);           \
-    }                                                                                          \
+  const bool kmask = L.kbias != nullptr;
+  // dQ first (it writes D), then dK/dV
+#define BWD_LAUNCH(T, C, D)                                                                   \
+  if (kmask) {                                                                                \
+    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, true>), grid, block, 0, st, a);                \
+    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, true>), grid, block, 0, st, a);              \
+  } else {                                                                                    \
+    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, false>), grid, block, 0, st, a);               \
+    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, false>), grid, block, 0, st, a);             \
+  }
+#define ATTN_BWD_LAUNCH(T)                                                                    \
+  if (L.causal) {                                                                             \
+    if (drop) { BWD_LAUNCH(T, true, true) } else { BWD_LAUNCH(T, true, false) }               \
+  } else {                                                                                    \
+    if (drop) { BWD_LAUNCH(T, false, true) } else { BWD_LAUNCH(T, false, false) }             \
   }
   if (L.dtype == DType::BF16) {
     ATTN_BWD_LAUNCH(bf16_t)
@@ -958,7 +1189,7 @@ void attn_bwd(const AttnBwdLaunch& L, hipStream_t st) {
     ATTN_BWD_LAUNCH(half_t)
   }
 #undef ATTN_BWD_LAUNCH
-#undef DQ_LAUNCH
+#undef BWD_LAUNCH
 }
 
 }  // namespace amd

@@ -472,9 +472,21 @@ struct AttnLaunch {
   int lse_stride;  // row stride of lse, a multiple of 64 (attn_lse_stride(S))
   bool causal;
   DType dtype;  // BF16 or F16
+  // prepared key mask (attn_prepare_key_mask), both null = none
+  const float* kbias = nullptr;          // [B][lse_stride]
+  const unsigned char* klive = nullptr;  // [B][lse_stride / 64]
 };
 int attn_lse_stride(int S);
 void attn_fwd(const AttnLaunch& L, hipStream_t st);
+
+// Per-batch key mask [B][S] -> the prepared pair the attention kernels read: an fp32
+// bias [B][Sp] (Sp = attn_lse_stride(S)) in log2 units, -inf on masked keys and on
+// columns >= S, and one liveness byte per (b, 64-key tile), 0 when the whole tile is
+// -inf.  Bool8: one byte per key, non-zero = masked; F32 / F16 / BF16: additive, added
+// to the scaled scores (-inf allowed).  One launch, no host sync.
+enum class AttnMaskKind : int { Bool8 = 0, F32 = 1, F16 = 2, BF16 = 3 };
+void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, float* bias,
+                           unsigned char* live, hipStream_t st);
 
 // backward: preprocess D = rowsum(dO*O), dK/dV kernel, dQ kernel (no atomics)
 struct AttnBwdLaunch {
@@ -496,6 +508,8 @@ struct AttnBwdLaunch {
   uint32_t seed;
   bool causal;
   DType dtype;
+  const float* kbias = nullptr;  // the forward's prepared key mask, or both null
+  const unsigned char* klive = nullptr;
 };
 void attn_bwd(const AttnBwdLaunch& L, hipStream_t st);
 

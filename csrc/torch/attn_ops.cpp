@@ -45,13 +45,70 @@ AttnLaunch make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tenso
   L.o = nullptr; L.lse = nullptr;
   return L;
 }
+
+// the prepared key mask of attn_prepare_key_mask_op for a [B, S, ...] call, or neither
+void check_key_mask(const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& live,
+                    const at::Tensor& q, int B, int Sp, const float** pb,
+                    const unsigned char** pl) {
+  *pb = nullptr;
+  *pl = nullptr;
+  TORCH_CHECK(bias.has_value() == live.has_value(),
+              "attn: key_bias and key_live come as a pair (attn.prepare_key_mask)");
+  if (!bias.has_value()) return;
+  const at::Tensor& kb = *bias;
+  const at::Tensor& kl = *live;
+  TORCH_CHECK(kb.is_cuda() && kl.is_cuda() && kb.device() == q.device() &&
+                  kl.device() == q.device(),
+              "attn: the prepared key mask must be on q's device");
+  TORCH_CHECK(kb.scalar_type() == at::kFloat && kb.dim() == 2 && kb.size(0) == B &&
+                  kb.size(1) == Sp && kb.is_contiguous(),
+              "attn: key_bias must be a contiguous fp32 [B, round_up(S, 64)] tensor, got ",
+              kb.sizes(), " for B = ", B, ", S = ", q.size(1));
+  TORCH_CHECK(kl.scalar_type() == at::kByte && kl.dim() == 2 && kl.size(0) == B &&
+                  kl.size(1) == Sp / 64 && kl.is_contiguous(),
+              "attn: key_live must be a contiguous uint8 [B, round_up(S, 64) / 64] tensor, got ",
+              kl.sizes());
+  TORCH_CHECK(((uintptr_t)kb.data_ptr() % 16) == 0, "attn: key_bias must be 16-byte aligned");
+  *pb = kb.data_ptr<float>();
+  *pl = kl.data_ptr<unsigned char>();
+}
 }  // namespace
+
+std::tuple<at::Tensor, at::Tensor> attn_prepare_key_mask_op(at::Tensor mask, int64_t S) {
+  c10::NoGradGuard no_grad_;
+  TORCH_CHECK(mask.is_cuda(), "attn.prepare_key_mask: the key mask must be a GPU tensor");
+  TORCH_CHECK(mask.dim() == 2 && mask.size(1) == S,
+              "attn.prepare_key_mask: the key mask must be [B, S] with S = ", S, ", got ",
+              mask.sizes());
+  TORCH_CHECK(mask.is_contiguous(), "attn.prepare_key_mask: the key mask must be contiguous");
+  TORCH_CHECK(S > 0 && S < (int64_t{1} << 24), "attn.prepare_key_mask: S out of range");
+  AttnMaskKind kind;
+  switch (mask.scalar_type()) {
+    case at::kBool:
+    case at::kByte: kind = AttnMaskKind::Bool8; break;
+    case at::kFloat: kind = AttnMaskKind::F32; break;
+    case at::kHalf: kind = AttnMaskKind::F16; break;
+    case at::kBFloat16: kind = AttnMaskKind::BF16; break;
+    default:
+      TORCH_CHECK(false, "attn.prepare_key_mask: bool / uint8 (non-zero = masked) or fp32 / "
+                         "fp16 / bf16 (additive) mask expected, got ", mask.scalar_type());
+  }
+  const int B = (int)mask.size(0), Sp = attn_lse_stride((int)S);
+  at::Tensor bias = at::empty({B, Sp}, mask.options().dtype(at::kFloat));
+  at::Tensor live = at::empty({B, Sp / 64}, mask.options().dtype(at::kByte));
+  if (B > 0)
+    attn_prepare_key_mask(mask.data_ptr(), kind, B, (int)S, bias.data_ptr<float>(),
+                          live.data_ptr<unsigned char>(), cur_stream());
+  return {bias, live};
+}
 
 std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::Tensor v,
                                                bool causal, double dropout, int64_t seed,
-                                               double scale) {
+                                               double scale, c10::optional<at::Tensor> key_bias,
+                                               c10::optional<at::Tensor> key_live) {
   c10::NoGradGuard no_grad_;
   AttnLaunch L = make_launch(q, k, v, causal, dropout, seed, scale);
+  check_key_mask(key_bias, key_live, q, L.B, L.lse_stride, &L.kbias, &L.klive);
   at::Tensor o = at::empty({L.B, L.S, L.H, 64}, q.options());
   at::Tensor lse = at::empty({L.B, L.H, L.lse_stride}, q.options().dtype(at::kFloat));
   L.o = o.data_ptr();
@@ -62,9 +119,11 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
 
 void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                  at::Tensor lse, bool causal, double dropout, int64_t seed, double scale,
-                 at::Tensor dq, at::Tensor dk, at::Tensor dv) {
+                 at::Tensor dq, at::Tensor dk, at::Tensor dv, c10::optional<at::Tensor> key_bias,
+                 c10::optional<at::Tensor> key_live) {
   c10::NoGradGuard no_grad_;
   AttnLaunch F = make_launch(q, k, v, causal, dropout, seed, scale);
+  check_key_mask(key_bias, key_live, q, F.B, F.lse_stride, &F.kbias, &F.klive);
   if (!(dout.dim() == 4 && view_ok(dout))) dout = dout.contiguous();
   if (!(o.dim() == 4 && view_ok(o))) o = o.contiguous();
   check_view(dout, "dout");
@@ -86,7 +145,8 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
     padded.narrow(2, 0, S).copy_(lse);
     lse = padded;
   }
-  at::Tensor D = at::empty({B, H, Sp}, lse.options());
+  // masked: D is followed by the dQ kernel's guarded copy of lse for the dK/dV kernel
+  at::Tensor D = at::empty({F.kbias ? 2 : 1, B, H, Sp}, lse.options());
   if (S == 0 || B * H == 0) return;
   AttnBwdLaunch L;
   L.q = F.q; L.k = F.k; L.v = F.v; L.o = o.data_ptr(); L.dout = dout.data_ptr();
@@ -103,6 +163,7 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   L.B = B; L.H = H; L.S = S;
   L.scale = F.scale; L.dropout = F.dropout; L.seed = F.seed;
   L.causal = causal; L.dtype = F.dtype;
+  L.kbias = F.kbias; L.klive = F.klive;
   attn_bwd(L, cur_stream());
 }
 

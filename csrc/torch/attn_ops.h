@@ -1,6 +1,7 @@
 // Torch bindings for the fused attention kernels (csrc/hip/attention.hip).
 #pragma once
 #include <ATen/ATen.h>
+#include <c10/util/Optional.h>
 
 #include <tuple>
 
@@ -9,14 +10,26 @@ namespace amd {
 // q, k, v: [B, S, H, 64] bf16/fp16 views (head dim contiguous, 16-B aligned rows).
 // Returns (o [B, S, H, 64] contiguous, lse [B, H, S] fp32 log2 units; a view of a
 // row-padded [B, H, round_up(S, 64)] buffer).
+// key_bias / key_live: the prepared key mask of attn_prepare_key_mask_op (both or neither).
 std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::Tensor v,
                                                bool causal, double dropout, int64_t seed,
-                                               double scale);
+                                               double scale,
+                                               c10::optional<at::Tensor> key_bias = c10::nullopt,
+                                               c10::optional<at::Tensor> key_live = c10::nullopt);
+
+// Per-batch key mask [B, S] (bool / uint8: non-zero = masked key; fp32 / fp16 / bf16:
+// additive, added to the scaled scores, -inf allowed) -> (bias fp32 [B, round_up(S, 64)]
+// in log2 units with -inf past S, live uint8 [B, round_up(S, 64) / 64]: 0 where a 64-key
+// tile is all -inf).  One launch, no host sync; reusable by every layer that shares the
+// mask and by the backward.
+std::tuple<at::Tensor, at::Tensor> attn_prepare_key_mask_op(at::Tensor mask, int64_t S);
 
 // Writes dq, dk, dv (caller-allocated [B, S, H, 64] views, e.g. slices of one
 // packed dqkv buffer) from dout, the forward inputs, o and lse.
 void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                  at::Tensor lse, bool causal, double dropout, int64_t seed, double scale,
-                 at::Tensor dq, at::Tensor dk, at::Tensor dv);
+                 at::Tensor dq, at::Tensor dk, at::Tensor dv,
+                 c10::optional<at::Tensor> key_bias = c10::nullopt,
+                 c10::optional<at::Tensor> key_live = c10::nullopt);
 
 }  // namespace amd

@@ -101,8 +101,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ln.def("bwd_one_row", &layer_norm_bwd_one_row_on);
 
   auto attn = m.def_submodule("attn", "fused attention (head dim 64, MFMA, gfx950)");
-  attn.def("fwd", &attn_fwd_op);
-  attn.def("bwd", &attn_bwd_op);
+  attn.def("fwd", &attn_fwd_op, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+           py::arg("dropout"), py::arg("seed"), py::arg("scale"),
+           py::arg("key_bias") = py::none(), py::arg("key_live") = py::none());
+  attn.def("bwd", &attn_bwd_op, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
+           py::arg("o"), py::arg("lse"), py::arg("causal"), py::arg("dropout"), py::arg("seed"),
+           py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
+           py::arg("key_bias") = py::none(), py::arg("key_live") = py::none());
+  attn.def("prepare_key_mask", &attn_prepare_key_mask_op, py::arg("mask"), py::arg("S"));
 
   auto dn = m.def_submodule("dense", "dense-layer bias gradients / fused GELU backward");
   dn.def("bias_grad", &bias_grad_op);
