@@ -58,8 +58,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> layer_norm_backward_op(
     at::Tensor t = rms ? dg - xh * s2 : dg - dg.mean(1, true) - xh * s2;
     at::Tensor dx = (t * invvar.unsqueeze(1)).to(x.scalar_type()).view(x.sizes());
     at::Tensor dgam, dbet;
-    if (need_wgrad && has(gamma)) dgam = (df * xh).sum(0).to(gamma->scalar_type());
-    if (need_bgrad && has(gamma)) dbet = df.sum(0).to(gamma->scalar_type());
+    // in the parameter's shape (normalized_shape may have several dimensions)
+    if (need_wgrad && has(gamma))
+      dgam = (df * xh).sum(0).to(gamma->scalar_type()).view(gamma->sizes());
+    if (need_bgrad && has(gamma))
+      dbet = df.sum(0).to(gamma->scalar_type()).view(gamma->sizes());
     return {dx, dgam, dbet};
   }
   at::Tensor g = has(gamma) ? gamma->contiguous() : at::Tensor();
@@ -70,6 +73,10 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> layer_norm_backward_op(
   if (need_bgrad && g.defined()) dbet = at::empty_like(g);
   if (dgam.defined() || dbet.defined())
     part = at::empty({layer_norm_bwd_workspace(n1, n2)}, x.options().dtype(at::kFloat));
+  if (n1 == 0) {  // no kernel runs: the parameter gradients are sums over no rows
+    if (dgam.defined()) dgam.zero_();
+    if (dbet.defined()) dbet.zero_();
+  }
   layer_norm_bwd(dy.data_ptr(), x.data_ptr(), dtype_of(x), g.defined() ? g.data_ptr() : nullptr,
                  tw, mean.data_ptr<float>(), invvar.data_ptr<float>(), dx.data_ptr(),
                  dgam.defined() ? dgam.data_ptr() : nullptr,
@@ -161,6 +168,11 @@ add_dropout_layer_norm_backward_op(at::Tensor dy, at::Tensor s, at::Tensor mean,
     dhs = at::empty_like(g);
   if (dgam.defined() || dbet.defined())
     part = at::empty({layer_norm_bwd_workspace(n1, n2)}, s.options().dtype(at::kFloat));
+  if (n1 == 0) {  // no kernel runs: the column sums are sums over no rows
+    if (dgam.defined()) dgam.zero_();
+    if (dbet.defined()) dbet.zero_();
+    if (dhs.defined()) dhs.zero_();
+  }
   LnFuse f = make_fuse(p, seed);
   f.dhsum = dhs.defined() ? dhs.data_ptr() : nullptr;
   f.dres = e.defined() ? e.data_ptr() : nullptr;
