@@ -32,27 +32,34 @@ def sdpa_masks(key_padding_mask, attn_mask, mask_additive, B, Tq, Tk, dtype, dev
     return m
 
 
+def _fused_key_mask(key_padding_mask, mask_additive, device):
+    """The modules' key-padding mask as the fused ops' keyword arguments."""
+    if key_padding_mask is None:
+        return {}
+    if isinstance(key_padding_mask, fused_attn.PreparedKeyMask):
+        return {"key_bias": key_padding_mask}
+    kp = key_padding_mask.to(device)
+    if mask_additive:
+        return {"key_bias": kp.float()}
+    return {"key_padding_mask": kp.bool()}
+
+
 def attention_bshd(q, k, v, dropout_p, key_padding_mask=None, attn_mask=None,
-                   mask_additive=False, allow_fused=True):
+                   mask_additive=False, allow_fused=True, kv=None):
     """q [B, Tq, H, D], k/v [B, Tk, H, D] (any strides) -> [B, Tq, H, D].
-    gfx950 fused kernels when eligible (no attn_mask, Tq == Tk, D == 64, 16-bit; a
-    key-padding mask - boolean / byte, or additive under ``mask_additive``, or an
-    ops.attention.PreparedKeyMask - is applied inside the kernels), PyTorch SDPA
-    otherwise."""
+    gfx950 fused kernels when eligible (no attn_mask, D == 64, 16-bit; Tq and Tk may
+    differ; a key-padding mask [B, Tk] - boolean / byte, or additive under
+    ``mask_additive``, or an ops.attention.PreparedKeyMask - is applied inside the
+    kernels), PyTorch SDPA otherwise.  ``kv``: the packed [B, Tk, 2, H, D] tensor that k
+    and v are the two halves of, when there is one: the fused path then takes it whole
+    (``fused_attention_kv``: one packed dkv in the backward); the SDPA path uses k and v."""
     B, Tq, H, D = q.shape
     Tk = k.size(1)
-    if allow_fused and attn_mask is None and Tq == Tk and fused_attn.supported(q, D):
-        if key_padding_mask is None:
-            return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p)
-        if isinstance(key_padding_mask, fused_attn.PreparedKeyMask):
-            return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p,
-                                              key_bias=key_padding_mask)
-        kp = key_padding_mask.to(q.device)
-        if mask_additive:
-            return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p,
-                                              key_bias=kp.float())
-        return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p,
-                                          key_padding_mask=kp.bool())
+    if allow_fused and attn_mask is None and fused_attn.supported(q, D):
+        mask_kw = _fused_key_mask(key_padding_mask, mask_additive, q.device)
+        if kv is not None:
+            return fused_attn.fused_attention_kv(q, kv, dropout_p=dropout_p, **mask_kw)
+        return fused_attn.fused_attention(q, k, v, causal=False, dropout_p=dropout_p, **mask_kw)
     mask = sdpa_masks(key_padding_mask, attn_mask, mask_additive, B, Tq, Tk, q.dtype, q.device)
     o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
                                        attn_mask=mask, dropout_p=dropout_p,

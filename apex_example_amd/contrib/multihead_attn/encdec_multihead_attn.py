@@ -2,8 +2,10 @@
 SURVEY.md A-24): time-first encoder-decoder attention, queries from ``query``
 [Tq, B, E] (``in_proj_weight_q``), keys / values from ``key`` [Tk, B, E]
 (fused ``in_proj_weight_kv``), optional fused pre-LayerNorm + residual add.
-The gfx950 fused attention kernels run when Tq == Tk and no mask is given;
-otherwise PyTorch SDPA.
+The gfx950 fused attention kernels (``ops.fused_attention_kv`` on the packed kv
+projection) run for any Tq and Tk, with or without a key-padding mask [B, Tk]
+(head dim 64, bf16 / fp16, ``impl="fast"``); an ``attn_mask`` [Tq, Tk] goes to PyTorch
+SDPA.
 """
 from __future__ import annotations
 
@@ -67,10 +69,12 @@ class EncdecMultiheadAttn(nn.Module):
         q = F.linear(x, self.in_proj_weight_q, self.in_proj_bias_q)
         kv = F.linear(key, self.in_proj_weight_kv, self.in_proj_bias_kv)
         q = q.view(Tq, B, self.num_heads, self.head_dim).transpose(0, 1)
-        k, v = kv.view(Tk, B, 2, self.num_heads, self.head_dim).permute(1, 0, 2, 3, 4).unbind(2)
+        # the packed projection output stays whole for the fused kernels (one packed dkv)
+        kv = kv.view(Tk, B, 2, self.num_heads, self.head_dim).permute(1, 0, 2, 3, 4)
+        k, v = kv.unbind(2)
         p = self.dropout if (is_training and self.training) else 0.0
         o = attention_bshd(q, k, v, p, key_padding_mask, attn_mask, False,
-                           allow_fused=(self.impl == "fast"))
+                           allow_fused=(self.impl == "fast"), kv=kv)
         out = F.linear(o.transpose(0, 1).reshape(Tq, B, E), self.out_proj_weight,
                        self.out_proj_bias)
         if self.include_norm_add:

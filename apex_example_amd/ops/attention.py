@@ -12,9 +12,14 @@ free); its backward writes dQ/dK/dV straight into ONE packed buffer, so the
 projection's input gradient needs no concatenation.  Layout-generic views
 ([S, B, ...] sequence-first included) work: the kernels take strides.
 
-Key masks: ``key_padding_mask`` ([B, S] bool, True = masked key, Apex's convention)
-or ``key_bias`` ([B, S] float, added to the scaled scores, ``-inf`` allowed) mask keys
-per batch element inside the kernels.  ``prepare_key_mask`` turns either into the
+Cross-attention: q may be [B, Sq, H, 64] against k / v of another length
+[B, Sk, H, 64] (``fused_attention``), and ``fused_attention_kv(q, kv)`` takes the packed
+[B, Sk, 2, H, 64] output of a fused KV projection, its backward writing dK/dV into ONE
+packed buffer of kv's layout.  The causal mask is defined for Sq == Sk only.
+
+Key masks: ``key_padding_mask`` ([B, S] bool with S the KEY length, True = masked key,
+Apex's convention) or ``key_bias`` ([B, S] float, added to the scaled scores, ``-inf``
+allowed) mask keys per batch element inside the kernels.  ``prepare_key_mask`` turns either into the
 form the kernels read (an fp32 bias row in log2 units plus one liveness byte per
 64-key tile) in one launch without a host sync; pass the returned ``PreparedKeyMask``
 in place of the mask to share it between the layers of a model.  64-key tiles whose
@@ -22,9 +27,10 @@ keys are all masked are skipped (no loads, no math) wherever they lie, masked ke
 get exactly zero dK / dV, and a query whose keys are all masked gets o = 0 and
 dq = 0 (its lse is unspecified) instead of NaN.
 
-Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64, q/k/v of one
-sequence length, no mask other than a per-batch key mask (a [Tq, Tk] ``attn_mask``
-is not fused).  Callers fall back to ``F.scaled_dot_product_attention`` otherwise.
+Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64, q and k / v of one
+batch size and head count (the query and key lengths may differ), no mask other than
+a per-batch key mask (a [Tq, Tk] ``attn_mask`` is not fused) or, at equal lengths, the
+causal mask.  Callers fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
 from __future__ import annotations
 
@@ -103,8 +109,9 @@ def prepare_key_mask(mask: torch.Tensor) -> PreparedKeyMask:
 
 
 def _key_mask(key_padding_mask, key_bias, like):
-    """The (bias, live) pair of a call's mask arguments for q ``like`` [B, S, H, 64], or
-    (None, None)."""
+    """The (bias, live) pair of a call's mask arguments for the keys ``like``
+    [B, S, ...] (k, or a packed qkv / kv whose dim 1 is the key length; ``q`` in the
+    messages), or (None, None)."""
     if key_padding_mask is None and key_bias is None:
         return None, None
     if key_padding_mask is not None and key_bias is not None:
@@ -123,16 +130,23 @@ def _key_mask(key_padding_mask, key_bias, like):
             raise ValueError("key mask is on %s, q on %s" % (m.device, like.device))
         m = prepare_key_mask(m)
     if (m.B, m.S) != (B, S):
-        raise ValueError("prepared key mask is for [B, S] = [%d, %d], q has [%d, %d]" % (
-            m.B, m.S, B, S))
+        raise ValueError("prepared key mask is for [B, S] = [%d, %d], the call's keys are "
+                         "[%d, %d]" % (m.B, m.S, B, S))
     if m.bias.device != like.device:
         raise ValueError("key mask is on %s, q on %s" % (m.bias.device, like.device))
     return m.bias, m.live
 
 
+def _check_causal(causal, Sq, Sk):
+    if causal and Sq != Sk:
+        raise ValueError("causal attention needs equal query and key lengths, got Sq = %d, "
+                         "Sk = %d" % (Sq, Sk))
+
+
 class FusedAttentionFunction(torch.autograd.Function):
     """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v on
-    [B, S, H, 64] views; (kbias, klive) is a prepared key mask or (None, None)."""
+    q [B, Sq, H, 64] and k, v [B, Sk, H, 64] views; (kbias, klive) is a prepared key mask
+    of the Sk keys or (None, None)."""
 
     @staticmethod
     def forward(ctx, q, k, v, causal, dropout_p, scale, seed, kbias=None, klive=None):
@@ -177,15 +191,55 @@ class FusedQKVAttentionFunction(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None
 
 
+class FusedKVAttentionFunction(torch.autograd.Function):
+    """Cross-attention on a packed key / value projection: q [B, Sq, H, 64] and kv
+    [B, Sk, 2, H, 64] (any strides) -> o [B, Sq, H, 64]; backward returns dq and one
+    packed dkv of kv's layout."""
+
+    @staticmethod
+    def forward(ctx, q, kv, dropout_p, scale, seed, kbias=None, klive=None):
+        k, v = kv.unbind(2)
+        o, lse = _C().fwd(q, k, v, False, float(dropout_p), int(seed), float(scale),
+                          kbias, klive)
+        ctx.save_for_backward(q, kv, o, lse, kbias, klive)
+        ctx.cfg = (float(dropout_p), int(seed), float(scale))
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, kv, o, lse, kbias, klive = ctx.saved_tensors
+        p, seed, scale = ctx.cfg
+        dq = torch.empty_like(q)  # q's own (dense) layout: a time-first projection gets
+        dkv = torch.empty_like(kv)  # its gradient back as a view, no transpose copy
+        k, v = kv.unbind(2)
+        dk, dv = dkv.unbind(2)
+        _C().bwd(do, q, k, v, o, lse, False, p, seed, scale, dq, dk, dv, kbias, klive)
+        return dq, dkv, None, None, None, None, None
+
+
 def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
                     key_bias=None):
-    """q, k, v: [B, S, H, 64] -> o [B, S, H, 64].  key_padding_mask: [B, S] bool, True =
-    masked key; key_bias: [B, S] float, added to the scaled scores; either may be a
+    """q: [B, Sq, H, 64], k, v: [B, Sk, H, 64] -> o [B, Sq, H, 64] (Sq != Sk is
+    cross-attention; ``causal`` needs Sq == Sk).  key_padding_mask: [B, Sk] bool, True =
+    masked key; key_bias: [B, Sk] float, added to the scaled scores; either may be a
     ``PreparedKeyMask``."""
+    _check_causal(causal, q.size(1), k.size(1))
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
-    kbias, klive = _key_mask(key_padding_mask, key_bias, q)
+    kbias, klive = _key_mask(key_padding_mask, key_bias, k)
     return FusedAttentionFunction.apply(q, k, v, causal, dropout_p, scale, _seed(dropout_p),
                                         kbias, klive)
+
+
+def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, key_bias=None):
+    """q: [B, Sq, H, 64], kv: [B, Sk, 2, H, 64] (the packed output of a fused KV
+    projection, any strides) -> o [B, Sq, H, 64]; the backward writes dK and dV into one
+    packed dkv of kv's layout.  Masks are [B, Sk], as in ``fused_attention``."""
+    if kv.dim() != 5 or kv.size(2) != 2:
+        raise ValueError("kv must be [B, Sk, 2, H, 64], got %s" % (tuple(kv.shape),))
+    scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
+    kbias, klive = _key_mask(key_padding_mask, key_bias, kv)
+    return FusedKVAttentionFunction.apply(q, kv, dropout_p, scale, _seed(dropout_p),
+                                          kbias, klive)
 
 
 def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,

@@ -2,12 +2,20 @@
 // causal mask and dropout): flash-attention style forward and backward on
 // v_mfma_f32_32x32x16_{bf16,f16}, written for CDNA4 rather than ported.
 //
-// Layouts: q, k, v are [B, S, H, 64] views with arbitrary batch / sequence /
-// head strides (e.g. slices of a fused qkv projection - no copies); o is written
-// as contiguous [B, S, H, 64] (so `.view(B, S, H*64)` is free); the gradients
-// go to caller-provided strided [B, S, H, 64] views (e.g. slices of one packed
-// dqkv buffer); lse is [B, H, Sp] fp32 in log2 units with the row stride Sp a
+// Layouts: q is a [B, Sq, H, 64] view, k and v are [B, Sk, H, 64] views, all with
+// arbitrary batch / sequence / head strides (e.g. slices of a fused qkv or kv
+// projection - no copies); o is written as contiguous [B, Sq, H, 64] (so
+// `.view(B, Sq, H*64)` is free); the gradients go to caller-provided strided views
+// shaped like q (dq) and k (dk, dv) (e.g. slices of one packed dqkv / dkv buffer);
+// lse is [B, H, Sp] fp32 in log2 units with the row stride Sp = Sq rounded up to a
 // multiple of 64 (so the backward can DMA 64-query tiles of it).
+//
+// Query and key lengths are separate wave-uniform scalars (cross-attention: a decoder
+// sequence over an encoder sequence).  Whatever bounds or indexes queries (the query
+// clamp, the o / lse / dq store guards, lse / D rows, the dK/dV query loop) takes Sq;
+// whatever bounds or indexes keys (the tile count, full-tile test and tail clamp of
+// the K/V ring, the key >= Sk mask, the dK/dV store guards, key-mask rows) takes Sk.
+// The causal mask is defined for Sq == Sk only.
 //
 // Forward (one wave = 32 queries, workgroup = 4 waves = 128 queries):
 //   * "swapped" QK^T: S^T = K . Q^T so a lane owns one query's scores (column
@@ -37,6 +45,7 @@
 // ride the K/V DMA ring; a dK/dV workgroup loads its lanes' biases once and writes
 // zeros when its 128 keys are all dead.  The KMASK=false instantiations are the
 // mask-free kernels unchanged.
+#include <cstdio>
 #include <cstdlib>
 
 #include "amd_dev.h"
@@ -228,15 +237,17 @@ struct AttnArgs {
   const void* k;
   const void* v;
   int64_t qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh;  // element strides
-  void* o;           // [B][S][H][64]
+  void* o;           // [B][Sq][H][64]
   float* lse;        // [B][H][lse_stride]
-  int B, H, S, lse_stride;
+  int B, H, Sq, Sk;  // query / key lengths (wave-uniform; causal: Sq == Sk)
+  int lse_stride;    // attn_lse_stride(Sq): rows of lse
+  int key_stride;    // attn_lse_stride(Sk): rows of kbias, 64 x the rows of klive
   float scale_log2;  // softmax scale * log2(e)
   uint32_t thr8;     // dropout threshold round(p * 256) on a hash byte, 0 = no dropout
   float inv_keep;    // 1 / (1 - p)
   uint32_t seed;
-  const float* kbias;          // KMASK: [B][lse_stride] log2-unit key bias
-  const unsigned char* klive;  // KMASK: [B][lse_stride / 64] tile liveness
+  const float* kbias;          // KMASK: [B][key_stride] log2-unit key bias
+  const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
 };
 
 // ------------------------------------------------------------------- key-mask prepare
@@ -312,6 +323,10 @@ __device__ __forceinline__ float max_halves(float x) {
 
 template <typename T, bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
+  // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
+  // read the one length and stride, so they are the single-length kernels unchanged
+  const int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
+  [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int KV = 2 * kAKT * kARow;          // K and V images of one tile
   constexpr int BUF = KV + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
@@ -335,15 +350,15 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   // Q^T fragments (B operand of S^T = K . Q^T): d = 16s + 8hl + j
   v8 qf[4];
   {
-    const int qq = q < a.S ? q : a.S - 1;
+    const int qq = q < Sq ? q : Sq - 1;
 #pragma unroll
     for (int s = 0; s < 4; ++s)
       qf[s] = *reinterpret_cast<const v8*>(Q + (int64_t)qq * a.qss + 16 * s + 8 * hl);
   }
 
-  int nkt = (a.S + kAKT - 1) / kAKT;
+  int nkt = (Sk + kAKT - 1) / kAKT;
   if (CAUSAL) {
-    const int last = (qb0 + 127 < a.S ? qb0 + 127 : a.S - 1) / kAKT + 1;
+    const int last = (qb0 + 127 < Sq ? qb0 + 127 : Sq - 1) / kAKT + 1;
     nkt = last < nkt ? last : nkt;
   }
   // DMA: each wave fills 16 rows of K and of V per tile (2 x 1 KiB instructions each)
@@ -355,14 +370,14 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
     kof[i] = row_off<T>(row, a.kss, (swz_rows(row, pch) - row * kARow) >> 4);  // logical chunk at pch
     vof[i] = row_off<T>(row, a.vss, (swz_tr(row, pch) - row * kARow) >> 4);
   }
-  const float* kbias = KMASK ? a.kbias + (int64_t)b * a.lse_stride : nullptr;
+  const float* kbias = KMASK ? a.kbias + (int64_t)b * kstride : nullptr;
   auto issue = [&](int kt, int buf) {
     unsigned char* Kl = lds + buf * BUF;
     unsigned char* Vl = Kl + kAKT * kARow;
     if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
       if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, Kl + KV);
     }
-    if ((kt + 1) * kAKT <= a.S) {
+    if ((kt + 1) * kAKT <= Sk) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
       const T* vb = tile_base(V, kt * kAKT, a.vss);
 #pragma unroll
@@ -376,7 +391,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
     for (int i = 0; i < 2; ++i) {
       const int row = (wid * 2 + i) * 8 + lrow;
       const int key = kt * kAKT + row;
-      const int kk = key < a.S ? key : a.S - 1;
+      const int kk = key < Sk ? key : Sk - 1;
       const int chk = (swz_rows(row, pch) - row * kARow) >> 4;  // logical chunk at pch
       const int chv = (swz_tr(row, pch) - row * kARow) >> 4;
       glds16(K + (int64_t)kk * a.kss + chk * 8, Kl + (wid * 2 + i) * 1024);
@@ -479,14 +494,14 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
       // mask (boundary / diagonal tiles only: the test is wave-uniform), running
       // max on the raw scores, then one fma + exp2 per score in log2 units
       const bool need_mask =
-          (k0 + kAKT > a.S) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+          (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
       if (need_mask) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
-            if (key >= a.S || (CAUSAL && key > q)) x[t][r] = -INFINITY;
+            if (key >= Sk || (CAUSAL && key > q)) x[t][r] = -INFINITY;
           }
       }
       float tmax = -INFINITY;
@@ -544,7 +559,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
       }
   };
   if constexpr (KMASK) {
-    LiveTiles lt(a.klive + (int64_t)b * (a.lse_stride / kAKT), nkt, lane);
+    LiveTiles lt(a.klive + (int64_t)b * (kstride / kAKT), nkt, lane);
     int kt = lt.next();
     if (kt < nkt) issue(kt, 0);
     for (int slot = 0; kt < nkt; slot ^= 1) {
@@ -559,8 +574,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
 
   const float lt = l + __shfl_xor(l, 32);
   const float inv = lt > 0.f ? (DROP ? a.inv_keep : 1.f) / lt : 0.f;
-  if (q < a.S) {
-    store_dT<T>(static_cast<T*>(a.o) + (((int64_t)b * a.S + q) * a.H + hh) * kAD, o, hl, inv);
+  if (q < Sq) {
+    store_dT<T>(static_cast<T*>(a.o) + (((int64_t)b * Sq + q) * a.H + hh) * kAD, o, hl, inv);
     if (hl == 0) a.lse[(int64_t)bh * a.lse_stride + q] = m + log2f(lt);
   }
 }
@@ -579,13 +594,15 @@ struct AttnBwdArgs {
   int64_t dqsb, dqss, dqsh, dksb, dkss, dksh, dvsb, dvss, dvsh;
   const float* lse;  // [B][H][lse_stride] log2 units
   float* D;          // [B][H][lse_stride] rowsum(dO * O); KMASK: [2][B][H][lse_stride]
-  int B, H, S, lse_stride;
+  int B, H, Sq, Sk;  // query / key lengths (wave-uniform; causal: Sq == Sk)
+  int lse_stride;    // attn_lse_stride(Sq): rows of lse, D and the lse copy behind D
+  int key_stride;    // attn_lse_stride(Sk): rows of kbias, 64 x the rows of klive
   float scale, scale_log2;
   uint32_t thr8;
   float inv_keep;
   uint32_t seed;
-  const float* kbias;          // KMASK: [B][lse_stride] log2-unit key bias
-  const unsigned char* klive;  // KMASK: [B][lse_stride / 64] tile liveness
+  const float* kbias;          // KMASK: [B][key_stride] log2-unit key bias
+  const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
 };
 
 // A query none of whose keys is live has lse = -inf (or whatever the caller stored);
@@ -606,6 +623,10 @@ __device__ __forceinline__ float lse_guard(float lse) { return lse == -INFINITY 
 // leaves, a wave whose 32 keys are all dead keeps the ring's barriers and skips the math.
 template <typename T, bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
+  // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
+  // read the one length and stride, so they are the single-length kernels unchanged
+  const int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
+  [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;     // 8 KiB
   constexpr int BUF = 4 * IMG + 1024;   // Q rows, Q tr, dO rows, dO tr, {lse, D}
@@ -619,15 +640,15 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   const int kb0 = tile * 128;
   const int kw0 = kb0 + wid * 32;
   const int key = kw0 + c32;
-  const int kk = key < a.S ? key : a.S - 1;
+  const int kk = key < Sk ? key : Sk - 1;
   float kbias = 0.f;
   bool wave_dead = false;
   if constexpr (KMASK) {
-    const int nlt = a.lse_stride / kAKT;
+    const int nlt = kstride / kAKT;
     const unsigned char* lv = a.klive + (int64_t)b * nlt;
     const int t0 = kb0 / kAKT;
     if (lv[t0] == 0 && (t0 + 1 >= nlt || lv[t0 + 1] == 0)) {
-      if (key < a.S) {
+      if (key < Sk) {
         T* dvp = static_cast<T*>(a.dv) + b * a.dvsb + (int64_t)key * a.dvss + hh * a.dvsh;
         T* dkp = static_cast<T*>(a.dk) + b * a.dksb + (int64_t)key * a.dkss + hh * a.dksh;
 #pragma unroll
@@ -638,7 +659,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
       }
       return;
     }
-    kbias = key < a.S ? a.kbias[(int64_t)b * a.lse_stride + key] : -INFINITY;
+    kbias = key < Sk ? a.kbias[(int64_t)b * kstride + key] : -INFINITY;
     wave_dead = !__any(kbias > -INFINITY);
   }
   // dropout lattice point of (query key & 3, this lane's key quad)
@@ -664,7 +685,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     }
   }
 
-  const int nqt = (a.S + kAKT - 1) / kAKT;
+  const int nqt = (Sq + kAKT - 1) / kAKT;
   const int qt0 = CAUSAL ? kb0 / kAKT : 0;
   const int lrow = lane >> 3, pch = lane & 7;
   auto issue = [&](int qt, int buf) {
@@ -680,7 +701,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     for (int i = 0; i < 2; ++i) {
       const int row = (wid * 2 + i) * 8 + lrow;
       const int qr = qt * kAKT + row;
-      const int qc = qr < a.S ? qr : a.S - 1;
+      const int qc = qr < Sq ? qr : Sq - 1;
       const int chr = (swz_rows(row, pch) - row * kARow) >> 4;
       const int cht = (swz_tr(row, pch) - row * kARow) >> 4;
       const T* qrow = Q + (int64_t)qc * a.qss;
@@ -781,7 +802,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int q = q0 + 32 * h + 8 * (r >> 2) + 4 * hl + (r & 3);
-        if (!(q < a.S && !(CAUSAL && key > q))) sc[r] = dp[r] = 0.f;
+        if (!(q < Sq && !(CAUSAL && key > q))) sc[r] = dp[r] = 0.f;
       }
     };
     auto accum = [&](int h, const f32x16_t& sc, const f32x16_t& dp) {
@@ -803,7 +824,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     // KMASK takes the half-by-half path always: the straight-line block sits at 246-256
     // VGPRs, and the bias on top of that spilled (1-33 VGPRs, reloaded inside the loop)
     // in whichever instantiation the register allocator liked least.
-    const bool clean = (q0 + kAKT <= a.S) && (!CAUSAL || kw0 + 31 <= q0);
+    const bool clean = (q0 + kAKT <= Sq) && (!CAUSAL || kw0 + 31 <= q0);
     if (!KMASK && clean) {
       f32x16_t sc0, dp0, sc1, dp1;
       sdp(0, sc0, dp0);
@@ -821,13 +842,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
         sdp(h, sc, dp);
         softmax_bwd(h, sc, dp);
         // wave-uniform: does any (query, key) of this 32 x 32 block need a mask?
-        if ((qh0 + 31 >= a.S) || (CAUSAL && kw0 + 31 > qh0)) mask(h, sc, dp);
+        if ((qh0 + 31 >= Sq) || (CAUSAL && kw0 + 31 > qh0)) mask(h, sc, dp);
         accum(h, sc, dp);
       }
     }
   }
 
-  if (key < a.S) {
+  if (key < Sk) {
     store_dT<T>(static_cast<T*>(a.dv) + b * a.dvsb + (int64_t)key * a.dvss + hh * a.dvsh, dv, hl,
                 DROP ? a.inv_keep : 1.f);
     store_dT<T>(static_cast<T*>(a.dk) + b * a.dksb + (int64_t)key * a.dkss + hh * a.dksh, dk, hl,
@@ -843,6 +864,10 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
 // dead tiles are skipped as in the forward.
 template <typename T, bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
+  // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
+  // read the one length and stride, so they are the single-length kernels unchanged
+  const int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
+  [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;
   constexpr int BUF = 3 * IMG + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
@@ -855,7 +880,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   const int b = bh / a.H, hh = bh - b * a.H;
   const int qb0 = tile * 128;
   const int q = qb0 + wid * 32 + c32;
-  const int qq = q < a.S ? q : a.S - 1;
+  const int qq = q < Sq ? q : Sq - 1;
   const uint32_t dbase = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)q * kDropQ +
                                     (uint32_t)hl * kDropK
                               : 0u;
@@ -890,15 +915,15 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     D_q = part + __shfl_xor(part, 32);
     if constexpr (KMASK) {  // D itself: refined at the end; here the guarded lse, so the
                             // dK/dV kernel need not guard per score
-      if (hl == 0 && q < a.S) a.D[((int64_t)a.B * a.H + bh) * a.lse_stride + q] = lse_q;
+      if (hl == 0 && q < Sq) a.D[((int64_t)a.B * a.H + bh) * a.lse_stride + q] = lse_q;
     } else {
-      if (hl == 0 && q < a.S) a.D[(int64_t)bh * a.lse_stride + q] = D_q;
+      if (hl == 0 && q < Sq) a.D[(int64_t)bh * a.lse_stride + q] = D_q;
     }
   }
 
-  int nkt = (a.S + kAKT - 1) / kAKT;
+  int nkt = (Sk + kAKT - 1) / kAKT;
   if (CAUSAL) {
-    const int last = (qb0 + 127 < a.S ? qb0 + 127 : a.S - 1) / kAKT + 1;
+    const int last = (qb0 + 127 < Sq ? qb0 + 127 : Sq - 1) / kAKT + 1;
     nkt = last < nkt ? last : nkt;
   }
   const int lrow = lane >> 3, pch = lane & 7;
@@ -912,13 +937,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     vro[i] = row_off<T>(row, a.vss, chr);
   }
   // images per buffer: 0 = K rows, 1 = K transposed, 2 = V rows[, 3 = bias]
-  const float* kbias = KMASK ? a.kbias + (int64_t)b * a.lse_stride : nullptr;
+  const float* kbias = KMASK ? a.kbias + (int64_t)b * kstride : nullptr;
   auto issue = [&](int kt, int buf) {
     unsigned char* base = lds + buf * BUF;
     if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
       if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, base + 3 * IMG);
     }
-    if ((kt + 1) * kAKT <= a.S) {
+    if ((kt + 1) * kAKT <= Sk) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
       const T* vb = tile_base(V, kt * kAKT, a.vss);
 #pragma unroll
@@ -934,7 +959,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     for (int i = 0; i < 2; ++i) {
       const int row = (wid * 2 + i) * 8 + lrow;
       const int kr = kt * kAKT + row;
-      const int kc = kr < a.S ? kr : a.S - 1;
+      const int kc = kr < Sk ? kr : Sk - 1;
       const int chr = (swz_rows(row, pch) - row * kARow) >> 4;
       const int cht = (swz_tr(row, pch) - row * kARow) >> 4;
       const T* krow = K + (int64_t)kc * a.kss;
@@ -974,7 +999,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       }
 
   // KMASK: kt walks the live tiles only (nx = the one after kt), the ring slot alternates
-  LiveTiles lt(KMASK ? a.klive + (int64_t)b * (a.lse_stride / kAKT) : nullptr, nkt, lane);
+  LiveTiles lt(KMASK ? a.klive + (int64_t)b * (kstride / kAKT) : nullptr, nkt, lane);
   int nx = 0, slot = 0;
   if constexpr (KMASK) {
     nx = lt.next();
@@ -1035,7 +1060,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
-        if (!(key < a.S && !(CAUSAL && key > q))) sc[r] = 0.f;
+        if (!(key < Sk && !(CAUSAL && key > q))) sc[r] = 0.f;
       }
     };
     auto accum = [&](int t, const f32x16_t& sc) {
@@ -1056,7 +1081,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     sdp(1, sc1, dp1);
     // wave-uniform; unmasked tiles run as one straight-line block (half 0's dQ MFMAs
     // beside half 1's softmax VALU)
-    const bool need_mask = (k0 + kAKT > a.S) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+    const bool need_mask = (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
     if (!need_mask) {
       dsoft(0, sc0, dp0);
       accum(0, sc0);
@@ -1073,9 +1098,9 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   }
   if constexpr (KMASK) {
     const float dD = dsum + __shfl_xor(dsum, 32);  // the two halves hold 32 keys each per tile
-    if (hl == 0 && q < a.S) a.D[(int64_t)bh * a.lse_stride + q] = D_q + dD;
+    if (hl == 0 && q < Sq) a.D[(int64_t)bh * a.lse_stride + q] = D_q + dD;
   }
-  if (q < a.S)
+  if (q < Sq)
     store_dT<T>(static_cast<T*>(a.dq) + b * a.dqsb + (int64_t)q * a.dqss + hh * a.dqsh, dq, hl,
                 a.scale);
 }
@@ -1111,20 +1136,31 @@ void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, fl
 #undef PREP_LAUNCH
 }
 
+// the causal mask is defined for one shared length only (no alignment convention for
+// unequal ones); the torch binding refuses the call before it gets here
+static void require_causal_square(const char* who, bool causal, int Sq, int Sk) {
+  if (causal && Sq != Sk) {
+    fprintf(stderr, "%s: causal needs equal query and key lengths, got Sq = %d, Sk = %d\n", who,
+            Sq, Sk);
+    abort();
+  }
+}
+
 void attn_fwd(const AttnLaunch& L, hipStream_t st) {
+  require_causal_square("attn_fwd", L.causal, L.Sq, L.Sk);
   AttnArgs a;
   a.q = L.q; a.k = L.k; a.v = L.v;
   a.qsb = L.qsb; a.qss = L.qss; a.qsh = L.qsh;
   a.ksb = L.ksb; a.kss = L.kss; a.ksh = L.ksh;
   a.vsb = L.vsb; a.vss = L.vss; a.vsh = L.vsh;
-  a.o = L.o; a.lse = L.lse; a.B = L.B; a.H = L.H; a.S = L.S;
-  a.lse_stride = L.lse_stride;
+  a.o = L.o; a.lse = L.lse; a.B = L.B; a.H = L.H; a.Sq = L.Sq; a.Sk = L.Sk;
+  a.lse_stride = L.lse_stride; a.key_stride = attn_lse_stride(L.Sk);
   a.scale_log2 = L.scale * 1.4426950408889634f;
   a.thr8 = drop_thr8(L.dropout);
   a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
   a.seed = L.seed;
   a.kbias = L.kbias; a.klive = L.klive;
-  dim3 grid((L.S + 127) / 128, L.B * L.H), block(kAT);
+  dim3 grid((L.Sq + 127) / 128, L.B * L.H), block(kAT);
   const bool drop = a.thr8 != 0;
   const bool kmask = L.kbias != nullptr;
 #define FWD_LAUNCH(T, C, D)                                                                   \
@@ -1146,6 +1182,7 @@ void attn_fwd(const AttnLaunch& L, hipStream_t st) {
 }
 
 void attn_bwd(const AttnBwdLaunch& L, hipStream_t st) {
+  require_causal_square("attn_bwd", L.causal, L.Sq, L.Sk);
   AttnBwdArgs a;
   a.q = L.q; a.k = L.k; a.v = L.v; a.o = L.o; a.dout = L.dout;
   a.qsb = L.qsb; a.qss = L.qss; a.qsh = L.qsh;
@@ -1157,25 +1194,27 @@ void attn_bwd(const AttnBwdLaunch& L, hipStream_t st) {
   a.dqsb = L.dqsb; a.dqss = L.dqss; a.dqsh = L.dqsh;
   a.dksb = L.dksb; a.dkss = L.dkss; a.dksh = L.dksh;
   a.dvsb = L.dvsb; a.dvss = L.dvss; a.dvsh = L.dvsh;
-  a.lse = L.lse; a.D = L.D; a.lse_stride = L.lse_stride;
-  a.B = L.B; a.H = L.H; a.S = L.S;
+  a.lse = L.lse; a.D = L.D;
+  a.lse_stride = L.lse_stride; a.key_stride = attn_lse_stride(L.Sk);
+  a.B = L.B; a.H = L.H; a.Sq = L.Sq; a.Sk = L.Sk;
   a.scale = L.scale;
   a.scale_log2 = L.scale * 1.4426950408889634f;
   a.thr8 = drop_thr8(L.dropout);
   a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
   a.seed = L.seed;
   a.kbias = L.kbias; a.klive = L.klive;
-  dim3 grid((L.S + 127) / 128, L.B * L.H), block(kAT);
+  // dQ owns 128-query tiles, dK/dV 128-key tiles
+  dim3 qgrid((L.Sq + 127) / 128, L.B * L.H), kgrid((L.Sk + 127) / 128, L.B * L.H), block(kAT);
   const bool drop = a.thr8 != 0;
   const bool kmask = L.kbias != nullptr;
   // dQ first (it writes D), then dK/dV
 #define BWD_LAUNCH(T, C, D)                                                                   \
   if (kmask) {                                                                                \
-    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, true>), grid, block, 0, st, a);                \
-    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, true>), grid, block, 0, st, a);              \
+    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, true>), qgrid, block, 0, st, a);               \
+    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, true>), kgrid, block, 0, st, a);             \
   } else {                                                                                    \
-    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, false>), grid, block, 0, st, a);               \
-    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, false>), grid, block, 0, st, a);             \
+    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, false>), qgrid, block, 0, st, a);              \
+    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, false>), kgrid, block, 0, st, a);            \
   }
 #define ATTN_BWD_LAUNCH(T)                                                                    \
   if (L.causal) {                                                                             \

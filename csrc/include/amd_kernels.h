@@ -463,18 +463,20 @@ struct AttnLaunch {
   const void* q;
   const void* k;
   const void* v;
-  int64_t qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh;  // element strides of [B,S,H,64] views
-  void* o;      // [B][S][H][64] contiguous
-  float* lse;   // [B][H][S]
-  int B, H, S;
+  // element strides of the [B,Sq,H,64] (q) and [B,Sk,H,64] (k, v) views
+  int64_t qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh;
+  void* o;      // [B][Sq][H][64] contiguous
+  float* lse;   // [B][H][Sq]
+  int B, H;
+  int Sq, Sk;   // query / key length, both > 0 at a launch
   float scale, dropout;
   uint32_t seed;
-  int lse_stride;  // row stride of lse, a multiple of 64 (attn_lse_stride(S))
-  bool causal;
+  int lse_stride;  // row stride of lse, a multiple of 64 (attn_lse_stride(Sq))
+  bool causal;     // Sq == Sk only
   DType dtype;  // BF16 or F16
-  // prepared key mask (attn_prepare_key_mask), both null = none
-  const float* kbias = nullptr;          // [B][lse_stride]
-  const unsigned char* klive = nullptr;  // [B][lse_stride / 64]
+  // prepared key mask (attn_prepare_key_mask) of the Sk keys, both null = none
+  const float* kbias = nullptr;          // [B][attn_lse_stride(Sk)]
+  const unsigned char* klive = nullptr;  // [B][attn_lse_stride(Sk) / 64]
 };
 int attn_lse_stride(int S);
 void attn_fwd(const AttnLaunch& L, hipStream_t st);
@@ -496,14 +498,15 @@ struct AttnBwdLaunch {
   const void* o;
   const void* dout;
   int64_t qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, dsb, dss, dsh;
-  void* dq;     // strided [B,S,H,64] outputs
+  void* dq;     // strided outputs: dq [B,Sq,H,64], dk / dv [B,Sk,H,64]
   void* dk;
   void* dv;
   int64_t dqsb, dqss, dqsh, dksb, dkss, dksh, dvsb, dvss, dvsh;
   const float* lse;  // [B][H][lse_stride]
-  float* D;          // workspace [B][H][lse_stride]
-  int lse_stride;
-  int B, H, S;
+  float* D;          // workspace [B][H][lse_stride], [2][B][H][lse_stride] with a key mask
+  int lse_stride;    // attn_lse_stride(Sq)
+  int B, H;
+  int Sq, Sk;        // as in AttnLaunch; dQ runs ceil(Sq/128) tiles, dK/dV ceil(Sk/128)
   float scale, dropout;
   uint32_t seed;
   bool causal;

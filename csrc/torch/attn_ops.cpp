@@ -1,6 +1,8 @@
 // Torch bindings for the fused attention kernels (csrc/hip/attention.hip).
 #include "attn_ops.h"
 
+#include <limits>
+
 #include "common.h"
 
 namespace amd {
@@ -23,33 +25,45 @@ bool view_ok(const at::Tensor& t) {
          t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0;
 }
 
+// q [B, Sq, H, 64], k / v [B, Sk, H, 64]: one B, H and dtype, any strides
 AttnLaunch make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                        bool causal, double dropout, int64_t seed, double scale) {
   check_view(q, "q");
   check_view(k, "k");
   check_view(v, "v");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(), "attn: q/k/v shapes differ");
+  TORCH_CHECK(v.sizes() == k.sizes(), "attn: k and v shapes differ: ", k.sizes(), " and ",
+              v.sizes());
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2),
+              "attn: q and k / v differ in batch or heads: q ", q.sizes(), ", k ", k.sizes(),
+              " (only the sequence length may differ)");
   TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type() &&
                   (q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf),
               "attn: bf16/fp16 q,k,v of one dtype");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
+              "attn: q, k and v must be on one device");
+  TORCH_CHECK(!causal || q.size(1) == k.size(1),
+              "attn: causal is defined for equal query and key lengths only, got Sq = ",
+              q.size(1), ", Sk = ", k.size(1));
   TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "attn: dropout must be in [0, 1)");
   AttnLaunch L;
   L.q = q.data_ptr(); L.k = k.data_ptr(); L.v = v.data_ptr();
   L.qsb = q.stride(0); L.qss = q.stride(1); L.qsh = q.stride(2);
   L.ksb = k.stride(0); L.kss = k.stride(1); L.ksh = k.stride(2);
   L.vsb = v.stride(0); L.vss = v.stride(1); L.vsh = v.stride(2);
-  L.B = (int)q.size(0); L.S = (int)q.size(1); L.H = (int)q.size(2);
+  L.B = (int)q.size(0); L.Sq = (int)q.size(1); L.Sk = (int)k.size(1); L.H = (int)q.size(2);
   L.scale = (float)scale; L.dropout = (float)dropout; L.seed = (uint32_t)seed;
   L.causal = causal; L.dtype = dtype_of(q);
-  L.lse_stride = attn_lse_stride(L.S);
+  L.lse_stride = attn_lse_stride(L.Sq);
   L.o = nullptr; L.lse = nullptr;
   return L;
 }
 
-// the prepared key mask of attn_prepare_key_mask_op for a [B, S, ...] call, or neither
+// the prepared key mask of attn_prepare_key_mask_op for the S = Sk keys of a call (Sp =
+// attn_lse_stride(Sk)), or neither
 void check_key_mask(const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& live,
-                    const at::Tensor& q, int B, int Sp, const float** pb,
+                    const at::Tensor& q, int B, int Sk, const float** pb,
                     const unsigned char** pl) {
+  const int Sp = attn_lse_stride(Sk);
   *pb = nullptr;
   *pl = nullptr;
   TORCH_CHECK(bias.has_value() == live.has_value(),
@@ -63,7 +77,7 @@ void check_key_mask(const c10::optional<at::Tensor>& bias, const c10::optional<a
   TORCH_CHECK(kb.scalar_type() == at::kFloat && kb.dim() == 2 && kb.size(0) == B &&
                   kb.size(1) == Sp && kb.is_contiguous(),
               "attn: key_bias must be a contiguous fp32 [B, round_up(S, 64)] tensor, got ",
-              kb.sizes(), " for B = ", B, ", S = ", q.size(1));
+              kb.sizes(), " for B = ", B, ", S = ", Sk, " keys");
   TORCH_CHECK(kl.scalar_type() == at::kByte && kl.dim() == 2 && kl.size(0) == B &&
                   kl.size(1) == Sp / 64 && kl.is_contiguous(),
               "attn: key_live must be a contiguous uint8 [B, round_up(S, 64) / 64] tensor, got ",
@@ -108,13 +122,18 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
                                                c10::optional<at::Tensor> key_live) {
   c10::NoGradGuard no_grad_;
   AttnLaunch L = make_launch(q, k, v, causal, dropout, seed, scale);
-  check_key_mask(key_bias, key_live, q, L.B, L.lse_stride, &L.kbias, &L.klive);
-  at::Tensor o = at::empty({L.B, L.S, L.H, 64}, q.options());
+  check_key_mask(key_bias, key_live, q, L.B, L.Sk, &L.kbias, &L.klive);
+  at::Tensor o = at::empty({L.B, L.Sq, L.H, 64}, q.options());
   at::Tensor lse = at::empty({L.B, L.H, L.lse_stride}, q.options().dtype(at::kFloat));
   L.o = o.data_ptr();
   L.lse = lse.data_ptr<float>();
-  if (L.S > 0 && L.B * L.H > 0) attn_fwd(L, cur_stream());
-  return {o, L.lse_stride == L.S ? lse : lse.narrow(2, 0, L.S)};
+  if (L.Sk == 0) {  // no key to attend to: o = 0, lse = log2(0), no launch
+    o.zero_();
+    lse.fill_(-std::numeric_limits<float>::infinity());
+  } else if (L.Sq > 0 && L.B * L.H > 0) {
+    attn_fwd(L, cur_stream());
+  }
+  return {o, L.lse_stride == L.Sq ? lse : lse.narrow(2, 0, L.Sq)};
 }
 
 void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
@@ -123,7 +142,7 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
                  c10::optional<at::Tensor> key_live) {
   c10::NoGradGuard no_grad_;
   AttnLaunch F = make_launch(q, k, v, causal, dropout, seed, scale);
-  check_key_mask(key_bias, key_live, q, F.B, F.lse_stride, &F.kbias, &F.klive);
+  check_key_mask(key_bias, key_live, q, F.B, F.Sk, &F.kbias, &F.klive);
   if (!(dout.dim() == 4 && view_ok(dout))) dout = dout.contiguous();
   if (!(o.dim() == 4 && view_ok(o))) o = o.contiguous();
   check_view(dout, "dout");
@@ -131,14 +150,22 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   check_view(dq, "dq");
   check_view(dk, "dk");
   check_view(dv, "dv");
-  for (const at::Tensor* t : {&dout, &o, &dq, &dk, &dv}) {
-    TORCH_CHECK(t->sizes() == q.sizes(), "attn bwd: shape mismatch");
+  for (const at::Tensor* t : {&dout, &o, &dq}) {
+    TORCH_CHECK(t->sizes() == q.sizes(), "attn bwd: shape mismatch: o, dout and dq must be "
+                "shaped like q ", q.sizes(), ", got ", t->sizes());
     TORCH_CHECK(t->scalar_type() == q.scalar_type(), "attn bwd: dtype mismatch");
   }
-  const int B = F.B, H = F.H, S = F.S, Sp = F.lse_stride;
+  for (const at::Tensor* t : {&dk, &dv}) {
+    TORCH_CHECK(t->sizes() == k.sizes(), "attn bwd: shape mismatch: dk and dv must be shaped "
+                "like k ", k.sizes(), ", got ", t->sizes());
+    TORCH_CHECK(t->scalar_type() == q.scalar_type(), "attn bwd: dtype mismatch");
+  }
+  for (const at::Tensor* t : {&dout, &o, &dq, &dk, &dv})
+    TORCH_CHECK(t->device() == q.device(), "attn bwd: every tensor must be on q's device");
+  const int B = F.B, H = F.H, S = F.Sq, Sp = F.lse_stride;
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 && lse.size(0) == B &&
-                  lse.size(1) == H && lse.size(2) == S,
-              "attn bwd: lse must be fp32 [B, H, S]");
+                  lse.size(1) == H && lse.size(2) == S && lse.device() == q.device(),
+              "attn bwd: lse must be fp32 [B, H, Sq] on q's device");
   if (!(lse.stride(2) == 1 && lse.stride(1) == Sp && lse.stride(0) == (int64_t)H * Sp &&
         ((uintptr_t)lse.data_ptr() % 16) == 0)) {
     at::Tensor padded = at::empty({B, H, Sp}, lse.options());
@@ -147,7 +174,16 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   }
   // masked: D is followed by the dQ kernel's guarded copy of lse for the dK/dV kernel
   at::Tensor D = at::empty({F.kbias ? 2 : 1, B, H, Sp}, lse.options());
-  if (S == 0 || B * H == 0) return;
+  if (B * H == 0) return;
+  if (F.Sk == 0) {  // no key: nothing reaches q
+    dq.zero_();
+    return;
+  }
+  if (S == 0) {  // no query: nothing reaches k / v
+    dk.zero_();
+    dv.zero_();
+    return;
+  }
   AttnBwdLaunch L;
   L.q = F.q; L.k = F.k; L.v = F.v; L.o = o.data_ptr(); L.dout = dout.data_ptr();
   L.qsb = F.qsb; L.qss = F.qss; L.qsh = F.qsh;
@@ -160,7 +196,7 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   L.dksb = dk.stride(0); L.dkss = dk.stride(1); L.dksh = dk.stride(2);
   L.dvsb = dv.stride(0); L.dvss = dv.stride(1); L.dvsh = dv.stride(2);
   L.lse = lse.data_ptr<float>(); L.D = D.data_ptr<float>(); L.lse_stride = Sp;
-  L.B = B; L.H = H; L.S = S;
+  L.B = B; L.H = H; L.Sq = S; L.Sk = F.Sk;
   L.scale = F.scale; L.dropout = F.dropout; L.seed = F.seed;
   L.causal = causal; L.dtype = F.dtype;
   L.kbias = F.kbias; L.klive = F.klive;

@@ -7,10 +7,13 @@
 
 namespace amd {
 
-// q, k, v: [B, S, H, 64] bf16/fp16 views (head dim contiguous, 16-B aligned rows).
-// Returns (o [B, S, H, 64] contiguous, lse [B, H, S] fp32 log2 units; a view of a
-// row-padded [B, H, round_up(S, 64)] buffer).
-// key_bias / key_live: the prepared key mask of attn_prepare_key_mask_op (both or neither).
+// q: [B, Sq, H, 64], k, v: [B, Sk, H, 64] bf16/fp16 views (head dim contiguous, 16-B
+// aligned rows; one B, H and dtype, the sequence lengths may differ - cross-attention).
+// Returns (o [B, Sq, H, 64] contiguous, lse [B, H, Sq] fp32 log2 units; a view of a
+// row-padded [B, H, round_up(Sq, 64)] buffer).  causal needs Sq == Sk.  Sk == 0 gives
+// o = 0 and lse = -inf without a launch.
+// key_bias / key_live: the prepared key mask of attn_prepare_key_mask_op for S = Sk (both
+// or neither).
 std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::Tensor v,
                                                bool causal, double dropout, int64_t seed,
                                                double scale,
@@ -24,8 +27,9 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
 // mask and by the backward.
 std::tuple<at::Tensor, at::Tensor> attn_prepare_key_mask_op(at::Tensor mask, int64_t S);
 
-// Writes dq, dk, dv (caller-allocated [B, S, H, 64] views, e.g. slices of one
-// packed dqkv buffer) from dout, the forward inputs, o and lse.
+// Writes dq (shaped like q), dk and dv (shaped like k; caller-allocated strided views,
+// e.g. slices of one packed dqkv or dkv buffer) from dout, the forward inputs, o and lse.
+// Sk == 0 writes dq = 0, Sq == 0 writes dk = dv = 0, both without a launch.
 void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                  at::Tensor lse, bool causal, double dropout, int64_t seed, double scale,
                  at::Tensor dq, at::Tensor dk, at::Tensor dv,

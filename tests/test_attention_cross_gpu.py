@@ -1,0 +1,502 @@
+"""Cross-attention in the fused attention kernels (csrc/hip/attention.hip): a query
+length Sq and a key length Sk that differ, against fp32 torch references generalised to
+[Sq, Sk] scores - plain and strided / packed-kv inputs, [B, Sk] key masks, dropout with the
+exact counter-hash keep mask, bitwise reproducibility, the equal-length path through the
+new arguments, the routing of EncdecMultiheadAttn, and argument validation.
+
+References and bounds are those of tests/test_attention_gpu.py and
+tests/test_attention_mask_gpu.py: o rtol = atol = 2e-2, lse 1e-3, gradients max-error /
+max-reference below 2e-2 (bf16) / 6e-3 (fp16), 3e-2 with dropout."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+NEG = float("-inf")
+DTYPES = [torch.bfloat16, torch.float16]
+
+
+def _C():
+    from apex_example_amd import _native
+
+    return _native.require().attn
+
+
+# ------------------------------------------------------------------ reference
+def ref_attention(q, k, v, bias=None, p=0.0, seed=0):
+    """fp32 reference on q [B, Sq, H, D], k / v [B, Sk, H, D] and an additive [B, Sk] key
+    bias -> (o [B, Sq, H, D], lse [B, H, Sq] log2, dead [B, H, Sq]: rows with no live key)."""
+    B, Sq, H, D = q.shape
+    Sk = k.size(1)
+    qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
+    s = qf @ kf.transpose(-1, -2) / math.sqrt(D)
+    if bias is not None:
+        s = s + bias.float().view(B, 1, 1, Sk)
+    dead = (s == NEG).all(-1, keepdim=True)
+    lse = torch.logsumexp(s, -1) / math.log(2.0)
+    pr = torch.softmax(torch.where(dead, torch.zeros_like(s), s), -1)
+    pr = torch.where(dead, torch.zeros_like(pr), pr)  # fully masked rows: p = 0, finite grads
+    if p > 0:
+        import dropout_hash
+
+        t = dropout_hash.thr8(p)
+        keep = dropout_hash.hash_bytes(B, H, Sq, seed, SK=Sk, device=q.device) >= t
+        pr = pr * keep * (256.0 / (256 - t))
+    return (pr @ vf).permute(0, 2, 1, 3), lse, dead.squeeze(-1)
+
+
+def _ref_grads(q, k, v, do, bias=None, p=0.0, seed=0):
+    qf, kf, vf = (t.detach().float().clone().requires_grad_(True) for t in (q, k, v))
+    o, _, _ = ref_attention(qf, kf, vf, bias, p=p, seed=seed)
+    o.backward(do.float())
+    return qf.grad, kf.grad, vf.grad
+
+
+def _close(a, b, rel, what="", floor=0.0):
+    """max |a - b| / max |b| < rel.  ``floor``: a lower limit of the denominator, for a
+    reference that is identically zero (see test_cross_fwd_bwd)."""
+    err = (a.float() - b).abs().max().item()
+    scale = max(b.abs().max().item(), floor) + 1e-6
+    print("%s max err %.3e / max magnitude %.3e = %.3e (bound %.1e)" % (
+        what, err, scale, err / scale, rel))
+    assert err / scale < rel, (what, err, scale)
+
+
+def _finite(*ts):
+    for t in ts:
+        assert torch.isfinite(t.float()).all()
+
+
+def _rel(dt):
+    return 2e-2 if dt == torch.bfloat16 else 6e-3
+
+
+def _inputs(B, Sq, Sk, H, dt, seed=0):
+    torch.manual_seed(seed)
+    q = torch.randn(B, Sq, H, 64, device=DEV, dtype=dt)
+    k = torch.randn(B, Sk, H, 64, device=DEV, dtype=dt)
+    v = torch.randn(B, Sk, H, 64, device=DEV, dtype=dt)
+    do = torch.randn(B, Sq, H, 64, device=DEV, dtype=dt)
+    return q, k, v, do
+
+
+def _run(q, k, v, do, **kw):
+    """fused_attention forward + backward on fresh leaves -> (o, dq, dk, dv)."""
+    from apex_example_amd.ops import fused_attention
+
+    q, k, v = (t.detach().clone().requires_grad_(True) for t in (q, k, v))
+    o = fused_attention(q, k, v, **kw)
+    o.backward(do)
+    return o.detach(), q.grad, k.grad, v.grad
+
+
+# ------------------------------------------------------- 1. fwd / bwd parity
+SHAPES = [
+    (2, 40, 200, 2),    # partial query tile, key tail tile
+    (2, 200, 40, 2),    # two query workgroups, one partial key tile, dK/dV query tail
+    (1, 128, 64, 1),    # everything aligned
+    (1, 1, 130, 3),     # a single query
+    (1, 130, 1, 1),     # a single key
+    (2, 300, 129, 2),   # a dK/dV workgroup owning one key, next liveness tile absent
+    (1, 64, 320, 1),    # more than four key tiles for one query wave
+]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("B,Sq,Sk,H", SHAPES)
+def test_cross_fwd_bwd(B, Sq, Sk, H, dt):
+    """Forward and all three gradients at unequal lengths.
+
+    A single key (Sk = 1) makes the softmax the constant 1: the reference's dq and dk are
+    identically zero (dS = p (dP - D) with D = dP), and the kernels' are the difference of
+    two fp32 sums of the same 64 products taken in different orders.  An error relative to
+    a zero maximum says nothing, so for these two gradients alone the denominator is the
+    size of the terms that cancel, max |dP| max |k| scale (dq) and max |dP| max |q| scale
+    (dk), dP = dO . v; dv (= the sum of dO over the queries) keeps the plain bound.
+    Measured at (1, 130, 1, 1): max |dq| 7.2e-7 (bf16) / 1.4e-6 (fp16) and max |dk| 1.2e-6 /
+    3.3e-6 where the reference is exactly 0 and the cancelling terms reach 7.7 and 10.7,
+    i.e. 9e-8 to 3e-7 of them."""
+    q, k, v, do = _inputs(B, Sq, Sk, H, dt)
+    o, lse = _C().fwd(q, k, v, False, 0.0, 0, 0.125)
+    assert o.shape == (B, Sq, H, 64) and lse.shape == (B, H, Sq)
+    ro, rlse, _ = ref_attention(q, k, v)
+    _finite(o, lse)
+    torch.testing.assert_close(o.float(), ro, rtol=2e-2, atol=2e-2)
+    torch.testing.assert_close(lse, rlse, rtol=1e-3, atol=1e-3)
+    o2, dq, dk, dv = _run(q, k, v, do)
+    assert torch.equal(o2, o)
+    assert dq.shape == q.shape and dk.shape == k.shape and dv.shape == v.shape
+    _finite(dq, dk, dv)
+    rq, rk, rv = _ref_grads(q, k, v, do)
+    fq = fk = 0.0
+    if Sk == 1:
+        assert rq.abs().max().item() == 0.0 and rk.abs().max().item() == 0.0
+        dp = (do.float() * v.float()).sum(-1).abs().max().item()
+        fq = dp * k.float().abs().max().item() * 0.125
+        fk = dp * q.float().abs().max().item() * 0.125
+    _close(dq, rq, _rel(dt), "dq", floor=fq)
+    _close(dk, rk, _rel(dt), "dk", floor=fk)
+    _close(dv, rv, _rel(dt), "dv")
+
+
+def test_empty_lengths():
+    """Sk == 0: o = 0 and dq = 0; Sq == 0: dk = dv = 0; no launch either way."""
+    q, k, v, do = _inputs(2, 40, 64, 2, torch.bfloat16)
+    o, dq, dk, dv = _run(q, k[:, :0], v[:, :0], do)
+    assert o.shape == q.shape and (o == 0).all() and (dq == 0).all()
+    assert dk.shape == (2, 0, 2, 64) and dv.shape == (2, 0, 2, 64)
+    o, dq, dk, dv = _run(q[:, :0], k, v, do[:, :0])
+    assert o.shape == (2, 0, 2, 64) and dq.shape == (2, 0, 2, 64)
+    assert dk.shape == k.shape and (dk == 0).all() and (dv == 0).all()
+
+
+# -------------------------------------------------------- 2. strided inputs
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("B,Sq,Sk,H", [(2, 40, 200, 2), (2, 200, 40, 2)])
+def test_cross_strided_module_layout(B, Sq, Sk, H, dt):
+    """q as a view of a time-first [Sq, B, H*64] projection, k / v the halves of a packed
+    time-first [Sk, B, 2, H, 64] tensor; fused_attention_kv's kv.grad has kv's layout."""
+    from apex_example_amd.ops import fused_attention, fused_attention_kv
+
+    torch.manual_seed(1)
+    qp = torch.randn(Sq, B, H * 64, device=DEV, dtype=dt, requires_grad=True)
+    kvp = torch.randn(Sk, B, 2 * H * 64, device=DEV, dtype=dt, requires_grad=True)
+    do = torch.randn(B, Sq, H, 64, device=DEV, dtype=dt)
+    q = qp.view(Sq, B, H, 64).transpose(0, 1)
+    kv = kvp.view(Sk, B, 2, H, 64).permute(1, 0, 2, 3, 4)
+    k, v = kv.unbind(2)
+    assert not q.is_contiguous() and not k.is_contiguous()
+    ro, _, _ = ref_attention(q.detach(), k.detach(), v.detach())
+    rq, rk, rv = _ref_grads(q, k, v, do)
+    results = []
+    for packed in (False, True):
+        qp.grad = kvp.grad = None
+        o = fused_attention_kv(q, kv) if packed else fused_attention(q, k, v)
+        o.backward(do)
+        assert o.shape == (B, Sq, H, 64)
+        torch.testing.assert_close(o.float(), ro, rtol=2e-2, atol=2e-2)
+        gq = qp.grad.view(Sq, B, H, 64).transpose(0, 1)
+        gkv = kvp.grad.view(Sk, B, 2, H, 64).permute(1, 0, 2, 3, 4)
+        _finite(o, gq, gkv)
+        _close(gq, rq, _rel(dt), "dq")
+        _close(gkv[:, :, 0], rk, _rel(dt), "dk")
+        _close(gkv[:, :, 1], rv, _rel(dt), "dv")
+        results.append((o.detach(), qp.grad.clone(), kvp.grad.clone()))
+    for a, b in zip(*results):  # the same kernels on the same values
+        assert torch.equal(a, b)
+    # the packed gradient itself: one tensor of kv's shape and layout
+    kv2 = kv.detach().requires_grad_(True)
+    fused_attention_kv(q.detach(), kv2).backward(do)
+    assert kv2.grad.shape == kv2.shape and kv2.grad.stride() == kv2.stride()
+    assert torch.equal(kv2.grad, results[1][2].view(Sk, B, 2, H, 64).permute(1, 0, 2, 3, 4))
+
+
+# ------------------------------------------------------------- 3. key masks
+MASK_SHAPES = [(3, 100, 200, 2), (2, 200, 100, 2)]
+MASK_FORMS = ["right", "left", "additive", "allmasked"]
+
+
+def make_bias(form, B, Sk):
+    """The additive [B, Sk] fp32 key bias of a mask form (CPU) and whether the form is a
+    boolean one (bias in {0, -inf}: key_padding_mask = bias == -inf)."""
+    g = torch.Generator().manual_seed(1234)
+    pos = torch.arange(Sk).view(1, Sk)
+    lens = torch.tensor([Sk, Sk * 2 // 3 + 4, Sk // 3][:B]).view(B, 1)  # per batch element
+    right = pos >= lens
+    if form == "right":
+        m = right
+    elif form == "left":        # the first 70 keys masked: the leading 64-key tile is dead
+        m = (pos < 70).expand(B, Sk)
+    elif form == "additive":    # -10000 on padded keys, small finite biases on live ones
+        return torch.where(right, torch.full((B, Sk), -10000.0),
+                           0.5 * torch.randn(B, Sk, generator=g)), False
+    elif form == "allmasked":   # one batch element with every key masked
+        m = right.clone()
+        m[B // 2] = True
+    else:
+        raise AssertionError(form)
+    return torch.zeros(B, Sk).masked_fill(m, NEG), True
+
+
+def _mask_kwargs(bias, boolean):
+    if boolean:
+        return {"key_padding_mask": (bias == NEG).to(DEV)}
+    return {"key_bias": bias.to(DEV)}
+
+
+_MASKED = {}
+
+
+def _masked_case(B, Sq, Sk, H, dt, form):
+    """Inputs, fused results and the fp32 reference of one masked case, computed once."""
+    key = (B, Sq, Sk, H, dt, form)
+    if key not in _MASKED:
+        bias, boolean = make_bias(form, B, Sk)
+        q, k, v, do = _inputs(B, Sq, Sk, H, dt)
+        kw = _mask_kwargs(bias, boolean)
+        o, dq, dk, dv = _run(q, k, v, do, **kw)
+        prep = _C().prepare_key_mask((bias == NEG).to(DEV) if boolean else bias.to(DEV), Sk)
+        _, lse = _C().fwd(q, k, v, False, 0.0, 0, 0.125, *prep)
+        bd = bias.to(DEV)
+        ro, rlse, dead = ref_attention(q, k, v, bd)
+        rq, rk, rv = _ref_grads(q, k, v, do, bd)
+        _MASKED[key] = dict(bias=bias, q=q, k=k, v=v, do=do, kw=kw, o=o, lse=lse, dq=dq, dk=dk,
+                            dv=dv, ro=ro, rlse=rlse, dead=dead, rq=rq, rk=rk, rv=rv)
+    return _MASKED[key]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("form", MASK_FORMS)
+@pytest.mark.parametrize("B,Sq,Sk,H", MASK_SHAPES)
+def test_cross_key_mask(B, Sq, Sk, H, form, dt):
+    c = _masked_case(B, Sq, Sk, H, dt, form)
+    assert c["lse"].shape == (B, H, Sq)
+    _finite(c["o"], c["dq"], c["dk"], c["dv"])
+    torch.testing.assert_close(c["o"].float(), c["ro"], rtol=2e-2, atol=2e-2)
+    live = ~c["dead"]
+    torch.testing.assert_close(c["lse"][live], c["rlse"][live], rtol=1e-3, atol=1e-3)
+    _close(c["dq"], c["rq"], _rel(dt), "dq")
+    _close(c["dk"], c["rk"], _rel(dt), "dk")
+    _close(c["dv"], c["rv"], _rel(dt), "dv")
+    gone = (c["bias"] == NEG).to(DEV)   # masked keys: exactly zero dk / dv
+    assert (c["dk"][gone] == 0).all() and (c["dv"][gone] == 0).all()
+    dead_rows = c["dead"].permute(0, 2, 1)  # [B, Sq, H]: queries with no live key
+    assert (c["o"][dead_rows] == 0).all() and (c["dq"][dead_rows] == 0).all()
+
+
+@pytest.mark.parametrize("B,Sq,Sk,H", MASK_SHAPES)
+def test_cross_all_masked_batch_element(B, Sq, Sk, H):
+    c = _masked_case(B, Sq, Sk, H, torch.bfloat16, "allmasked")
+    b = B // 2
+    assert c["dead"][b].all()
+    for t in (c["o"], c["dq"], c["dk"], c["dv"]):
+        assert (t[b] == 0).all()
+        assert torch.isfinite(t.float()).all()
+
+
+@pytest.mark.parametrize("B,Sq,Sk,H", MASK_SHAPES)
+def test_cross_prepared_mask_shared_by_two_calls(B, Sq, Sk, H):
+    from apex_example_amd.ops import fused_attention_kv, prepare_key_mask
+
+    c = _masked_case(B, Sq, Sk, H, torch.bfloat16, "right")
+    pm = prepare_key_mask(c["kw"]["key_padding_mask"])
+    assert (pm.B, pm.S) == (B, Sk)
+    assert pm.bias.shape == (B, (Sk + 63) // 64 * 64)
+    for kw in ({"key_padding_mask": pm}, {"key_bias": pm}):
+        o, dq, dk, dv = _run(c["q"], c["k"], c["v"], c["do"], **kw)
+        for a, b in zip((o, dq, dk, dv), (c["o"], c["dq"], c["dk"], c["dv"])):
+            assert torch.equal(a, b)
+    kv = torch.stack((c["k"], c["v"]), 2).requires_grad_(True)
+    o = fused_attention_kv(c["q"], kv, key_bias=pm)
+    o.backward(c["do"])
+    assert torch.equal(o, c["o"])
+    assert torch.equal(kv.grad[:, :, 0], c["dk"]) and torch.equal(kv.grad[:, :, 1], c["dv"])
+
+
+# --------------------------------------------------------------- 4. dropout
+def _dropout_case(B, Sq, Sk, H, lens=None):
+    from apex_example_amd.ops.attention import FusedAttentionFunction, prepare_key_mask
+
+    p, seed = 0.1, 4321
+    q, k, v, do = _inputs(B, Sq, Sk, H, torch.bfloat16, seed=2)
+    q, k, v = (t.requires_grad_(True) for t in (q, k, v))
+    bias, prep, gone = None, (None, None), None
+    if lens is not None:
+        gone = (torch.arange(Sk).view(1, Sk) >= torch.tensor(lens).view(B, 1)).to(DEV)
+        bias = torch.zeros(B, Sk, device=DEV).masked_fill(gone, NEG)
+        pm = prepare_key_mask(gone)
+        prep = (pm.bias, pm.live)
+    o = FusedAttentionFunction.apply(q, k, v, False, p, 0.125, seed, *prep)
+    o.backward(do)
+    ro, _, _ = ref_attention(q.detach(), k.detach(), v.detach(), bias, p=p, seed=seed)
+    rq, rk, rv = _ref_grads(q, k, v, do, bias, p=p, seed=seed)
+    _finite(o, q.grad, k.grad, v.grad)
+    torch.testing.assert_close(o.detach().float(), ro, rtol=3e-2, atol=3e-2)
+    _close(q.grad, rq, 3e-2, "dq")
+    _close(k.grad, rk, 3e-2, "dk")
+    _close(v.grad, rv, 3e-2, "dv")
+    if gone is not None:
+        assert (k.grad[gone] == 0).all() and (v.grad[gone] == 0).all()
+
+
+@pytest.mark.parametrize("B,Sq,Sk,H", [(2, 96, 160, 2), (2, 160, 96, 2)])
+def test_cross_dropout_exact_keep_mask(B, Sq, Sk, H):
+    _dropout_case(B, Sq, Sk, H)
+
+
+def test_cross_dropout_exact_keep_mask_right_padding():
+    _dropout_case(2, 96, 160, 2, lens=[160, 100])
+
+
+# ------------------------------------------------- 5. bitwise reproducibility
+def test_cross_deterministic():
+    from apex_example_amd.ops.attention import FusedAttentionFunction, prepare_key_mask
+
+    B, Sq, Sk, H = 2, 200, 136, 2
+    q, k, v, do = _inputs(B, Sq, Sk, H, torch.bfloat16, seed=3)
+    q, k, v = (t.requires_grad_(True) for t in (q, k, v))
+    gone = (torch.arange(Sk).view(1, Sk) >= torch.tensor([136, 70]).view(B, 1)).to(DEV)
+    pm = prepare_key_mask(gone)
+    runs = []
+    for _ in range(2):
+        for t in (q, k, v):
+            t.grad = None
+        o = FusedAttentionFunction.apply(q, k, v, False, 0.1, 0.125, 99, pm.bias, pm.live)
+        o.backward(do)
+        runs.append([o.detach().clone()] + [t.grad.clone() for t in (q, k, v)])
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+# ------------------------------- 6. equal lengths through the new arguments
+@pytest.mark.parametrize("p,masked", [(0.0, False), (0.1, True)])
+def test_equal_lengths_kv_path_matches_qkv(p, masked):
+    """Sq == Sk through fused_attention_kv (separate q, packed kv halves of the same
+    buffer) is bit for bit fused_attention_qkv on the packed data."""
+    from apex_example_amd.ops import fused_attention_kv, fused_attention_qkv
+
+    B, S, H = 2, 200, 2
+    torch.manual_seed(4)
+    qkv = torch.randn(B, S, 3, H, 64, device=DEV, dtype=torch.bfloat16)
+    do = torch.randn(B, S, H, 64, device=DEV, dtype=torch.bfloat16)
+    kw = {}
+    if masked:
+        gone = torch.arange(S).view(1, S) >= torch.tensor([200, 131]).view(B, 1)
+        kw = {"key_padding_mask": gone.to(DEV)}
+    a = qkv.clone().requires_grad_(True)
+    torch.manual_seed(5)   # the dropout seed is drawn from torch's CPU generator
+    oa = fused_attention_qkv(a, dropout_p=p, **kw)
+    oa.backward(do)
+    b = qkv.clone().requires_grad_(True)
+    torch.manual_seed(5)
+    ob = fused_attention_kv(b[:, :, 0], b[:, :, 1:], dropout_p=p, **kw)
+    ob.backward(do)
+    assert torch.equal(oa, ob)
+    assert torch.equal(a.grad, b.grad)
+
+
+# ---------------------------------------------------------------- 7. routing
+def _no_sdpa(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("F.scaled_dot_product_attention was called")
+
+    monkeypatch.setattr(F, "scaled_dot_product_attention", boom)
+
+
+def _encdec_pair(**kw):
+    from apex_example_amd.contrib.multihead_attn import EncdecMultiheadAttn
+
+    torch.manual_seed(0)
+    fast = EncdecMultiheadAttn(128, 2, bias=True, **kw).to(DEV).to(torch.bfloat16)
+    ref = EncdecMultiheadAttn(128, 2, bias=True, impl="default", **kw).to(DEV).to(
+        torch.bfloat16)
+    ref.load_state_dict(fast.state_dict())
+    return fast, ref
+
+
+@pytest.mark.parametrize("masked,norm_add", [(False, False), (True, False), (True, True)])
+def test_encdec_mha_unequal_lengths_take_fused_path(monkeypatch, masked, norm_add):
+    Tq, Tk, B = 70, 200, 3
+    fast, ref = _encdec_pair(include_norm_add=norm_add)
+    torch.manual_seed(1)
+    x = torch.randn(Tq, B, 128, device=DEV, dtype=torch.bfloat16)
+    m = torch.randn(Tk, B, 128, device=DEV, dtype=torch.bfloat16)
+    kpm = None
+    if masked:
+        kpm = (torch.arange(Tk).view(1, Tk) >= torch.tensor([200, 137, 65]).view(B, 1)).to(DEV)
+    xa, xr = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
+    ma, mr = m.clone().requires_grad_(True), m.clone().requires_grad_(True)
+    yr, _ = ref(xr, mr, key_padding_mask=kpm, is_training=False)
+    dy = torch.randn_like(yr)
+    yr.backward(dy)
+    _no_sdpa(monkeypatch)
+    ya, _ = fast(xa, ma, key_padding_mask=kpm, is_training=False)
+    ya.backward(dy)
+    assert ya.shape == (Tq, B, 128)
+    torch.testing.assert_close(ya.float(), yr.float(), rtol=2e-2, atol=2e-2)
+    _close(xa.grad, xr.grad.float(), 3e-2, "query grad")
+    _close(ma.grad, mr.grad.float(), 3e-2, "key grad")
+    _close(fast.in_proj_weight_kv.grad, ref.in_proj_weight_kv.grad.float(), 3e-2,
+           "in_proj_weight_kv grad")
+
+
+def test_encdec_mha_attn_mask_still_reaches_sdpa(monkeypatch):
+    Tq, Tk, B = 70, 200, 3
+    fast, _ = _encdec_pair()
+    x = torch.randn(Tq, B, 128, device=DEV, dtype=torch.bfloat16)
+    m = torch.randn(Tk, B, 128, device=DEV, dtype=torch.bfloat16)
+    am = torch.zeros(Tq, Tk, device=DEV, dtype=torch.bool)
+    am[:, 150:] = True
+    y, _ = fast(x, m, attn_mask=am, is_training=False)   # works through SDPA
+    assert torch.isfinite(y.float()).all()
+    _no_sdpa(monkeypatch)
+    with pytest.raises(AssertionError, match="scaled_dot_product_attention was called"):
+        fast(x, m, attn_mask=am, is_training=False)
+
+
+def test_attention_bshd_unequal_lengths_all_mask_forms(monkeypatch):
+    """The shared core with Tq != Tk: no mask, boolean, additive and prepared key-padding
+    masks all run fused (SDPA patched out) and agree with the fp32 reference."""
+    from apex_example_amd.contrib.multihead_attn._common import attention_bshd
+    from apex_example_amd.ops import prepare_key_mask
+
+    B, Tq, Tk, H = 3, 70, 200, 2
+    q, k, v, _ = _inputs(B, Tq, Tk, H, torch.bfloat16)
+    gone = (torch.arange(Tk).view(1, Tk) >= torch.tensor([200, 137, 65]).view(B, 1)).to(DEV)
+    add = torch.zeros(B, Tk, device=DEV).masked_fill(gone, NEG)
+    _no_sdpa(monkeypatch)
+    o = attention_bshd(q, k, v, 0.0)
+    torch.testing.assert_close(o.float(), ref_attention(q, k, v)[0], rtol=2e-2, atol=2e-2)
+    ro = ref_attention(q, k, v, add)[0]
+    for kpm, additive in ((gone, False), (add, True), (prepare_key_mask(gone), False)):
+        o = attention_bshd(q, k, v, 0.0, kpm, None, additive)
+        torch.testing.assert_close(o.float(), ro, rtol=2e-2, atol=2e-2)
+
+
+# ------------------------------------------------------------- 8. validation
+def test_cross_argument_validation():
+    from apex_example_amd.ops import fused_attention, fused_attention_kv
+
+    B, Sq, Sk, H = 2, 64, 128, 1
+    q, k, v, _ = _inputs(B, Sq, Sk, H, torch.bfloat16)
+    with pytest.raises(ValueError, match="causal"):
+        fused_attention(q, k, v, causal=True)
+    with pytest.raises(ValueError, match=r"\[B, S\]"):
+        fused_attention(q, k, v, key_padding_mask=torch.zeros(B, Sq, dtype=torch.bool,
+                                                              device=DEV))
+    with pytest.raises(ValueError, match=r"\[B, S\]"):
+        fused_attention_kv(q, torch.stack((k, v), 2), key_bias=torch.zeros(B, Sq, device=DEV))
+    with pytest.raises(ValueError, match="kv must be"):
+        fused_attention_kv(q, k)
+    with pytest.raises(RuntimeError, match="batch or heads"):
+        fused_attention(q, k[:1], v[:1])
+    with pytest.raises(RuntimeError, match="batch or heads"):
+        fused_attention(q, k.repeat(1, 1, 2, 1), v.repeat(1, 1, 2, 1))
+
+
+def test_cross_binding_validation():
+    C = _C()
+    B, Sq, Sk, H = 2, 64, 128, 1
+    q, k, v, do = _inputs(B, Sq, Sk, H, torch.bfloat16)
+    with pytest.raises(RuntimeError, match="causal"):
+        C.fwd(q, k, v, True, 0.0, 0, 0.125)
+    with pytest.raises(RuntimeError, match="batch or heads"):
+        C.fwd(q, k[:1], v[:1], False, 0.0, 0, 0.125)
+    with pytest.raises(RuntimeError, match="k and v shapes differ"):
+        C.fwd(q, k, v[:, :64], False, 0.0, 0, 0.125)
+    # a prepared mask of the QUERY length is not the call's key mask
+    kb, live = C.prepare_key_mask(torch.zeros(B, Sq, dtype=torch.bool, device=DEV), Sq)
+    with pytest.raises(RuntimeError, match="key_bias must be"):
+        C.fwd(q, k, v, False, 0.0, 0, 0.125, kb, live)
+    o, lse = C.fwd(q, k, v, False, 0.0, 0, 0.125)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    with pytest.raises(RuntimeError, match="shaped like k"):
+        C.bwd(do, q, k, v, o, lse, False, 0.0, 0, 0.125, dq, torch.empty_like(q), dv)
+    with pytest.raises(RuntimeError, match="shaped like q"):
+        C.bwd(do, q, k, v, o, lse, False, 0.0, 0, 0.125, torch.empty_like(k), dk, dv)
+    with pytest.raises(RuntimeError, match="causal"):
+        C.bwd(do, q, k, v, o, lse, True, 0.0, 0, 0.125, dq, dk, dv)

@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """Times the fused attention kernels with and without a key-padding mask against the
-SDPA fallback, at BERT-large's attention shape (docs/PERF.md "Key-padding masks").
+SDPA fallback, at BERT-large's attention shape (docs/PERF.md "Key-padding masks"), or
+with `--seq-k` at a cross-attention shape: a [B, seq] query side against a [B, seq-k]
+key side (docs/PERF.md "Cross-attention").
 
     python tools/attn_mask_bench.py                    # masked fused vs SDPA, padding sweep
+    python tools/attn_mask_bench.py --seq 128 --seq-k 512   # the same, decoder over encoder
     python tools/attn_mask_bench.py --raw [--so PATH]  # mask-free raw kernel calls only;
                                                        # --so times another build's _C
 
@@ -62,6 +65,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)   # bench.py's bert_large per-GPU batch
     ap.add_argument("--seq", type=int, default=512)
+    ap.add_argument("--seq-k", type=int, default=None,
+                    help="key-side length (default: --seq); the query side is --seq")
     ap.add_argument("--heads", type=int, default=16)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--windows", type=int, default=5)
@@ -71,18 +76,30 @@ def main():
     ap.add_argument("--so", default=None)
     a = ap.parse_args()
     B, S, H = a.batch, a.seq, a.heads
+    cross = a.seq_k is not None
+    Sk = a.seq_k if cross else S
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    qkv = torch.randn(B, S, 3, H, 64, device=dev, dtype=torch.bfloat16)
     do = torch.randn(B, S, H, 64, device=dev, dtype=torch.bfloat16)
     t = lambda fn: timed(fn, a.iters, a.windows, a.warmup)  # noqa: E731
     cfg = dict(B=B, S=S, H=H, dropout=a.dropout)
+    if cross:
+        # the layouts of a q projection and a fused kv projection
+        cfg["Sk"] = Sk
+        qx = torch.randn(B, S, H, 64, device=dev, dtype=torch.bfloat16)
+        kvx = torch.randn(B, Sk, 2, H, 64, device=dev, dtype=torch.bfloat16)
+    else:
+        qkv = torch.randn(B, S, 3, H, 64, device=dev, dtype=torch.bfloat16)
 
     if a.raw:
         C = load_ext(a.so).attn
-        q, k, v = qkv.unbind(2)
-        dqkv = torch.empty_like(qkv)
-        dq, dk, dv = dqkv.unbind(2)
+        if cross:
+            q, (k, v) = qx, kvx.unbind(2)
+            dq = torch.empty_like(qx)
+            dk, dv = torch.empty_like(kvx).unbind(2)
+        else:
+            q, k, v = qkv.unbind(2)
+            dq, dk, dv = torch.empty_like(qkv).unbind(2)
 
         def raw():
             o, lse = C.fwd(q, k, v, False, a.dropout, 11, 0.125)
@@ -91,30 +108,52 @@ def main():
         report("fused_mask_free_raw", t(raw), so=a.so or "in-tree", **cfg)
         return
 
-    from apex_example_amd.ops.attention import fused_attention_qkv, prepare_key_mask
+    from apex_example_amd.ops.attention import (fused_attention_kv, fused_attention_qkv,
+                                                prepare_key_mask)
 
-    x = qkv.clone().requires_grad_(True)
+    if cross:
+        xq, xkv = qx.clone().requires_grad_(True), kvx.clone().requires_grad_(True)
 
-    def run_fused(pm):
-        x.grad = None
-        fused_attention_qkv(x, dropout_p=a.dropout, key_bias=pm).backward(do)
+        def run_fused(pm):
+            xq.grad = xkv.grad = None
+            fused_attention_kv(xq, xkv, dropout_p=a.dropout, key_bias=pm).backward(do)
 
-    def run_sdpa(mask):  # the model's fallback path on the same packed qkv
-        x.grad = None
-        q, k, v = x.permute(2, 0, 3, 1, 4).unbind(0)
-        o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=a.dropout)
-        o.transpose(1, 2).backward(do)
+        def run_sdpa(mask):  # the fallback path on the same q and packed kv
+            xq.grad = xkv.grad = None
+            k, v = xkv.permute(2, 0, 3, 1, 4).unbind(0)
+            o = F.scaled_dot_product_attention(xq.transpose(1, 2), k, v, attn_mask=mask,
+                                               dropout_p=a.dropout)
+            o.transpose(1, 2).backward(do)
+    else:
+        x = qkv.clone().requires_grad_(True)
 
-    report("fused_mask_free", t(lambda: run_fused(None)), **cfg)
+        def run_fused(pm):
+            x.grad = None
+            fused_attention_qkv(x, dropout_p=a.dropout, key_bias=pm).backward(do)
+
+        def run_sdpa(mask):  # the model's fallback path on the same packed qkv
+            x.grad = None
+            q, k, v = x.permute(2, 0, 3, 1, 4).unbind(0)
+            o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=a.dropout)
+            o.transpose(1, 2).backward(do)
+
+    fu = t(lambda: run_fused(None))
+    report("fused_mask_free", fu, **cfg)
+    if cross:  # equal lengths: docs/PERF.md "Fused attention" has the mask-free comparison
+        sd = t(lambda: run_sdpa(None))
+        report("sdpa_mask_free", sd, **cfg)
+        report("ratio_sdpa_over_fused", {"ratio": round(sd["ms_median"] / fu["ms_median"], 3)},
+               padding="none")
     g = torch.Generator().manual_seed(0)
-    sweeps = [("uniform[128,512]", torch.randint(S // 4, S + 1, (B,), generator=g))]
-    sweeps += [("len=%d" % n, torch.full((B,), n)) for n in (S, 3 * S // 4, S // 2, S // 4)]
+    sweeps = [("uniform[%d,%d]" % (Sk // 4, Sk),
+               torch.randint(Sk // 4, Sk + 1, (B,), generator=g))]
+    sweeps += [("len=%d" % n, torch.full((B,), n)) for n in (Sk, 3 * Sk // 4, Sk // 2, Sk // 4)]
     for label, lens in sweeps:
-        keep = torch.arange(S).view(1, S) < lens.view(B, 1)
+        keep = torch.arange(Sk).view(1, Sk) < lens.view(B, 1)
         add = ((1.0 - keep.float()) * -10000.0).to(dev)   # BERT's additive convention
         report("prepare_key_mask", t(lambda: prepare_key_mask(add)), padding=label, **cfg)
         pm = prepare_key_mask(add)
-        mask = add.to(torch.bfloat16).view(B, 1, 1, S)
+        mask = add.to(torch.bfloat16).view(B, 1, 1, Sk)
         fu = t(lambda: run_fused(pm))
         sd = t(lambda: run_sdpa(mask))
         report("fused_masked", fu, padding=label, mean_len=float(lens.float().mean()), **cfg)
