@@ -143,78 +143,63 @@ def _check_causal(causal, Sq, Sk):
                          "Sk = %d" % (Sq, Sk))
 
 
-class FusedAttentionFunction(torch.autograd.Function):
-    """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v on
-    q [B, Sq, H, 64] and k, v [B, Sk, H, 64] views; (kbias, klive) is a prepared key mask
-    of the Sk keys or (None, None)."""
+# How a call's tensor inputs split into the q [B, Sq, H, 64] and k, v [B, Sk, H, 64] views
+# the kernels take; the gradient buffers, one per input, split the same way.
+_SPLIT = {
+    "qkv": lambda ts: ts,                                # q, k, v
+    "packed_qkv": lambda ts: ts[0].unbind(2),            # qkv [B, S, 3, H, 64]
+    "q_packed_kv": lambda ts: (ts[0], *ts[1].unbind(2)),  # q, kv [B, Sk, 2, H, 64]
+}
+
+
+class AttentionFunction(torch.autograd.Function):
+    """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v -> [B, Sq, H, 64]
+    on the q / k / v views of ``inputs`` (any strides) under ``layout``, a key of ``_SPLIT``;
+    (kbias, klive) is a prepared key mask of the Sk keys or (None, None).  The backward
+    returns one gradient per input: packed inputs (and the q beside a packed kv: a
+    time-first projection gets its gradient back as a view, no transpose copy) get theirs
+    in their own layout, separate q, k, v dense ones."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, dropout_p, scale, seed, kbias=None, klive=None):
-        o, lse = _C().fwd(q, k, v, bool(causal), float(dropout_p), int(seed), float(scale),
-                          kbias, klive)
-        ctx.save_for_backward(q, k, v, o, lse, kbias, klive)
-        ctx.cfg = (bool(causal), float(dropout_p), int(seed), float(scale))
+    def forward(ctx, layout, causal, dropout_p, scale, seed, kbias, klive, *inputs):
+        q, k, v = _SPLIT[layout](inputs)
+        ctx.cfg = (layout, bool(causal), float(dropout_p), int(seed), float(scale))
+        o, lse = _C().fwd(q, k, v, *ctx.cfg[1:], kbias, klive)
+        ctx.save_for_backward(*inputs, o, lse, kbias, klive)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, kbias, klive = ctx.saved_tensors
-        causal, p, seed, scale = ctx.cfg
-        dq = torch.empty_like(q, memory_format=torch.contiguous_format)
-        dk = torch.empty_like(k, memory_format=torch.contiguous_format)
-        dv = torch.empty_like(v, memory_format=torch.contiguous_format)
-        _C().bwd(do, q, k, v, o, lse, causal, p, seed, scale, dq, dk, dv, kbias, klive)
-        return dq, dk, dv, None, None, None, None, None, None
+        *inputs, o, lse, kbias, klive = ctx.saved_tensors
+        layout, *cfg = ctx.cfg
+        if layout == "qkv":
+            grads = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in inputs]
+        else:
+            grads = [torch.empty_like(t) for t in inputs]
+        _C().bwd(do, *_SPLIT[layout](inputs), o, lse, *cfg, *_SPLIT[layout](grads), kbias, klive)
+        return (None,) * 7 + tuple(grads)
 
 
-class FusedQKVAttentionFunction(torch.autograd.Function):
-    """Packed variant: qkv [B, S, 3, H, 64] (any strides) -> o [B, S, H, 64];
-    backward returns one packed dqkv of qkv's layout."""
-
+# The per-layout names, each ``.apply`` in its own argument order.
+class FusedAttentionFunction:
     @staticmethod
-    def forward(ctx, qkv, causal, dropout_p, scale, seed, kbias=None, klive=None):
-        q, k, v = qkv.unbind(2)
-        o, lse = _C().fwd(q, k, v, bool(causal), float(dropout_p), int(seed), float(scale),
-                          kbias, klive)
-        ctx.save_for_backward(qkv, o, lse, kbias, klive)
-        ctx.cfg = (bool(causal), float(dropout_p), int(seed), float(scale))
-        return o
+    def apply(q, k, v, causal, dropout_p, scale, seed, kbias=None, klive=None):
+        return AttentionFunction.apply("qkv", causal, dropout_p, scale, seed, kbias, klive,
+                                       q, k, v)
 
+
+class FusedQKVAttentionFunction:
     @staticmethod
-    def backward(ctx, do):
-        qkv, o, lse, kbias, klive = ctx.saved_tensors
-        causal, p, seed, scale = ctx.cfg
-        dqkv = torch.empty_like(qkv)
-        q, k, v = qkv.unbind(2)
-        dq, dk, dv = dqkv.unbind(2)
-        _C().bwd(do, q, k, v, o, lse, causal, p, seed, scale, dq, dk, dv, kbias, klive)
-        return dqkv, None, None, None, None, None, None
+    def apply(qkv, causal, dropout_p, scale, seed, kbias=None, klive=None):
+        return AttentionFunction.apply("packed_qkv", causal, dropout_p, scale, seed, kbias,
+                                       klive, qkv)
 
 
-class FusedKVAttentionFunction(torch.autograd.Function):
-    """Cross-attention on a packed key / value projection: q [B, Sq, H, 64] and kv
-    [B, Sk, 2, H, 64] (any strides) -> o [B, Sq, H, 64]; backward returns dq and one
-    packed dkv of kv's layout."""
-
+class FusedKVAttentionFunction:
     @staticmethod
-    def forward(ctx, q, kv, dropout_p, scale, seed, kbias=None, klive=None):
-        k, v = kv.unbind(2)
-        o, lse = _C().fwd(q, k, v, False, float(dropout_p), int(seed), float(scale),
-                          kbias, klive)
-        ctx.save_for_backward(q, kv, o, lse, kbias, klive)
-        ctx.cfg = (float(dropout_p), int(seed), float(scale))
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        q, kv, o, lse, kbias, klive = ctx.saved_tensors
-        p, seed, scale = ctx.cfg
-        dq = torch.empty_like(q)  # q's own (dense) layout: a time-first projection gets
-        dkv = torch.empty_like(kv)  # its gradient back as a view, no transpose copy
-        k, v = kv.unbind(2)
-        dk, dv = dkv.unbind(2)
-        _C().bwd(do, q, k, v, o, lse, False, p, seed, scale, dq, dk, dv, kbias, klive)
-        return dq, dkv, None, None, None, None, None
+    def apply(q, kv, dropout_p, scale, seed, kbias=None, klive=None):
+        return AttentionFunction.apply("q_packed_kv", False, dropout_p, scale, seed, kbias,
+                                       klive, q, kv)
 
 
 def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
@@ -244,8 +229,11 @@ def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, 
 
 def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
                         key_bias=None):
-    """qkv: [B, S, 3, H, 64] -> o [B, S, H, 64]; masks as in ``fused_attention``."""
+    """qkv: [B, S, 3, H, 64] (any strides) -> o [B, S, H, 64]; the backward returns one
+    packed dqkv of qkv's layout.  Masks as in ``fused_attention``."""
     scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
     kbias, klive = _key_mask(key_padding_mask, key_bias, qkv)
     return FusedQKVAttentionFunction.apply(qkv, causal, dropout_p, scale, _seed(dropout_p),
                                            kbias, klive)
+
+

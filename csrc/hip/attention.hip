@@ -47,6 +47,7 @@
 // mask-free kernels unchanged.
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "amd_dev.h"
 #include "amd_kernels.h"
@@ -1146,89 +1147,76 @@ static void require_causal_square(const char* who, bool causal, int Sq, int Sk) 
   }
 }
 
-void attn_fwd(const AttnLaunch& L, hipStream_t st) {
-  require_causal_square("attn_fwd", L.causal, L.Sq, L.Sk);
-  AttnArgs a;
-  a.q = L.q; a.k = L.k; a.v = L.v;
-  a.qsb = L.qsb; a.qss = L.qss; a.qsh = L.qsh;
-  a.ksb = L.ksb; a.kss = L.kss; a.ksh = L.ksh;
-  a.vsb = L.vsb; a.vss = L.vss; a.vsh = L.vsh;
-  a.o = L.o; a.lse = L.lse; a.B = L.B; a.H = L.H; a.Sq = L.Sq; a.Sk = L.Sk;
-  a.lse_stride = L.lse_stride; a.key_stride = attn_lse_stride(L.Sk);
-  a.scale_log2 = L.scale * 1.4426950408889634f;
-  a.thr8 = drop_thr8(L.dropout);
+namespace {
+
+// The kernel arguments a problem determines, for either direction (A = AttnArgs or
+// AttnBwdArgs, which name these fields alike): views, lengths, the two row strides and
+// the quantised dropout.  The caller adds its direction's buffers.
+template <typename A>
+A kernel_args(const char* who, const AttnProblem& p) {
+  require_causal_square(who, p.causal, p.Sq, p.Sk);
+  A a{};
+  a.q = p.q.p; a.qsb = p.q.sb; a.qss = p.q.ss; a.qsh = p.q.sh;
+  a.k = p.k.p; a.ksb = p.k.sb; a.kss = p.k.ss; a.ksh = p.k.sh;
+  a.v = p.v.p; a.vsb = p.v.sb; a.vss = p.v.ss; a.vsh = p.v.sh;
+  a.B = p.B; a.H = p.H; a.Sq = p.Sq; a.Sk = p.Sk;
+  a.lse_stride = attn_lse_stride(p.Sq);
+  a.key_stride = attn_lse_stride(p.Sk);
+  a.scale_log2 = p.scale * 1.4426950408889634f;
+  a.thr8 = drop_thr8(p.dropout);
   a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
-  a.seed = L.seed;
-  a.kbias = L.kbias; a.klive = L.klive;
-  dim3 grid((L.Sq + 127) / 128, L.B * L.H), block(kAT);
-  const bool drop = a.thr8 != 0;
-  const bool kmask = L.kbias != nullptr;
-#define FWD_LAUNCH(T, C, D)                                                                   \
-  if (kmask) hipLaunchKernelGGL((attn_fwd_k<T, C, D, true>), grid, block, 0, st, a);          \
-  else hipLaunchKernelGGL((attn_fwd_k<T, C, D, false>), grid, block, 0, st, a)
-#define ATTN_FWD_LAUNCH(T)                                                                    \
-  if (L.causal) {                                                                             \
-    if (drop) { FWD_LAUNCH(T, true, true); } else { FWD_LAUNCH(T, true, false); }             \
-  } else {                                                                                    \
-    if (drop) { FWD_LAUNCH(T, false, true); } else { FWD_LAUNCH(T, false, false); }           \
-  }
-  if (L.dtype == DType::BF16) {
-    ATTN_FWD_LAUNCH(bf16_t)
-  } else {
-    ATTN_FWD_LAUNCH(half_t)
-  }
-#undef ATTN_FWD_LAUNCH
-#undef FWD_LAUNCH
+  a.seed = p.seed;
+  a.kbias = p.kbias; a.klive = p.klive;
+  return a;
 }
 
-void attn_bwd(const AttnBwdLaunch& L, hipStream_t st) {
-  require_causal_square("attn_bwd", L.causal, L.Sq, L.Sk);
-  AttnBwdArgs a;
-  a.q = L.q; a.k = L.k; a.v = L.v; a.o = L.o; a.dout = L.dout;
-  a.qsb = L.qsb; a.qss = L.qss; a.qsh = L.qsh;
-  a.ksb = L.ksb; a.kss = L.kss; a.ksh = L.ksh;
-  a.vsb = L.vsb; a.vss = L.vss; a.vsh = L.vsh;
-  a.osb = L.osb; a.oss = L.oss; a.osh = L.osh;
-  a.dsb = L.dsb; a.dss = L.dss; a.dsh = L.dsh;
-  a.dq = L.dq; a.dk = L.dk; a.dv = L.dv;
-  a.dqsb = L.dqsb; a.dqss = L.dqss; a.dqsh = L.dqsh;
-  a.dksb = L.dksb; a.dkss = L.dkss; a.dksh = L.dksh;
-  a.dvsb = L.dvsb; a.dvss = L.dvss; a.dvsh = L.dvsh;
-  a.lse = L.lse; a.D = L.D;
-  a.lse_stride = L.lse_stride; a.key_stride = attn_lse_stride(L.Sk);
-  a.B = L.B; a.H = L.H; a.Sq = L.Sq; a.Sk = L.Sk;
-  a.scale = L.scale;
-  a.scale_log2 = L.scale * 1.4426950408889634f;
-  a.thr8 = drop_thr8(L.dropout);
-  a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
-  a.seed = L.seed;
-  a.kbias = L.kbias; a.klive = L.klive;
-  // dQ owns 128-query tiles, dK/dV 128-key tiles
-  dim3 qgrid((L.Sq + 127) / 128, L.B * L.H), kgrid((L.Sk + 127) / 128, L.B * L.H), block(kAT);
-  const bool drop = a.thr8 != 0;
-  const bool kmask = L.kbias != nullptr;
-  // dQ first (it writes D), then dK/dV
-#define BWD_LAUNCH(T, C, D)                                                                   \
-  if (kmask) {                                                                                \
-    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, true>), qgrid, block, 0, st, a);               \
-    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, true>), kgrid, block, 0, st, a);             \
-  } else {                                                                                    \
-    hipLaunchKernelGGL((attn_bwd_dq_k<T, C, D, false>), qgrid, block, 0, st, a);              \
-    hipLaunchKernelGGL((attn_bwd_dkdv_k<T, C, D, false>), kgrid, block, 0, st, a);            \
-  }
-#define ATTN_BWD_LAUNCH(T)                                                                    \
-  if (L.causal) {                                                                             \
-    if (drop) { BWD_LAUNCH(T, true, true) } else { BWD_LAUNCH(T, true, false) }               \
-  } else {                                                                                    \
-    if (drop) { BWD_LAUNCH(T, false, true) } else { BWD_LAUNCH(T, false, false) }             \
-  }
-  if (L.dtype == DType::BF16) {
-    ATTN_BWD_LAUNCH(bf16_t)
-  } else {
-    ATTN_BWD_LAUNCH(half_t)
-  }
-#undef ATTN_BWD_LAUNCH
-#undef BWD_LAUNCH
+template <typename T> struct Elem { using type = T; };
+
+// f(Elem<T>, causal, drop, kmask), the three switches as std::bool_constants: the
+// 2 x 2 x 2 x 2 kernel instantiations over a problem's dtype and options
+template <typename F>
+void dispatch(const AttnProblem& p, bool drop, F f) {
+  auto flag = [](bool on, auto g) { on ? g(std::true_type{}) : g(std::false_type{}); };
+  auto flags = [&](auto t) {
+    flag(p.causal, [&](auto c) {
+      flag(drop, [&](auto d) { flag(p.kbias != nullptr, [&](auto m) { f(t, c, d, m); }); });
+    });
+  };
+  if (p.dtype == DType::BF16) flags(Elem<bf16_t>{});
+  else flags(Elem<half_t>{});
 }
+
+// the kernel `name` instantiated for dispatch's (t, c, d, m)
+#define ATTN_KERNEL(name) \
+  name<typename decltype(t)::type, decltype(c)::value, decltype(d)::value, decltype(m)::value>
+
+}  // namespace
+
+void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
+  AttnArgs a = kernel_args<AttnArgs>("attn_fwd", p);
+  a.o = o; a.lse = lse;
+  dim3 grid((p.Sq + 127) / 128, p.B * p.H), block(kAT);
+  dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m) {
+    hipLaunchKernelGGL((ATTN_KERNEL(attn_fwd_k)), grid, block, 0, st, a);
+  });
+}
+
+void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
+  AttnBwdArgs a = kernel_args<AttnBwdArgs>("attn_bwd", p);
+  a.o = g.o.p; a.osb = g.o.sb; a.oss = g.o.ss; a.osh = g.o.sh;
+  a.dout = g.dout.p; a.dsb = g.dout.sb; a.dss = g.dout.ss; a.dsh = g.dout.sh;
+  a.dq = g.dq.p; a.dqsb = g.dq.sb; a.dqss = g.dq.ss; a.dqsh = g.dq.sh;
+  a.dk = g.dk.p; a.dksb = g.dk.sb; a.dkss = g.dk.ss; a.dksh = g.dk.sh;
+  a.dv = g.dv.p; a.dvsb = g.dv.sb; a.dvss = g.dv.ss; a.dvsh = g.dv.sh;
+  a.lse = g.lse; a.D = g.D;
+  a.scale = p.scale;
+  // dQ owns 128-query tiles, dK/dV 128-key tiles; dQ first (it writes D), then dK/dV
+  dim3 qgrid((p.Sq + 127) / 128, p.B * p.H), kgrid((p.Sk + 127) / 128, p.B * p.H), block(kAT);
+  dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m) {
+    hipLaunchKernelGGL((ATTN_KERNEL(attn_bwd_dq_k)), qgrid, block, 0, st, a);
+    hipLaunchKernelGGL((ATTN_KERNEL(attn_bwd_dkdv_k)), kgrid, block, 0, st, a);
+  });
+}
+#undef ATTN_KERNEL
 
 }  // namespace amd

@@ -459,27 +459,29 @@ void colsum(const void* x, const void* pre, void* out_dpre, DType t, int64_t M, 
             int act_mode, float* part, int S, void* bias_grad, DType tb, hipStream_t st);
 
 // ---- fused attention, head dim 64 (attention.hip) ---------------------------
-struct AttnLaunch {
-  const void* q;
-  const void* k;
-  const void* v;
-  // element strides of the [B,Sq,H,64] (q) and [B,Sk,H,64] (k, v) views
-  int64_t qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh;
-  void* o;      // [B][Sq][H][64] contiguous
-  float* lse;   // [B][H][Sq]
+// A [B, S, H, 64] tensor with a contiguous head dim: pointer and element strides.
+struct AttnView {
+  void* p = nullptr;
+  int64_t sb = 0, ss = 0, sh = 0;  // batch, sequence, head
+};
+// One attention problem, shared by the forward and the backward.
+struct AttnProblem {
+  AttnView q, k, v;  // q [B,Sq,H,64], k / v [B,Sk,H,64]
   int B, H;
-  int Sq, Sk;   // query / key length, both > 0 at a launch
+  int Sq, Sk;        // query / key length, both > 0 at a launch
   float scale, dropout;
   uint32_t seed;
-  int lse_stride;  // row stride of lse, a multiple of 64 (attn_lse_stride(Sq))
-  bool causal;     // Sq == Sk only
-  DType dtype;  // BF16 or F16
+  bool causal;       // Sq == Sk only
+  DType dtype;       // BF16 or F16
   // prepared key mask (attn_prepare_key_mask) of the Sk keys, both null = none
   const float* kbias = nullptr;          // [B][attn_lse_stride(Sk)]
   const unsigned char* klive = nullptr;  // [B][attn_lse_stride(Sk) / 64]
 };
+// Row stride of lse / D (S = Sq) and of the prepared key mask (S = Sk): S rounded up to
+// a multiple of 64.
 int attn_lse_stride(int S);
-void attn_fwd(const AttnLaunch& L, hipStream_t st);
+// o [B][Sq][H][64] contiguous, lse [B][H][attn_lse_stride(Sq)]
+void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st);
 
 // Per-batch key mask [B][S] -> the prepared pair the attention kernels read: an fp32
 // bias [B][Sp] (Sp = attn_lse_stride(S)) in log2 units, -inf on masked keys and on
@@ -490,31 +492,16 @@ enum class AttnMaskKind : int { Bool8 = 0, F32 = 1, F16 = 2, BF16 = 3 };
 void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, float* bias,
                            unsigned char* live, hipStream_t st);
 
-// backward: preprocess D = rowsum(dO*O), dK/dV kernel, dQ kernel (no atomics)
-struct AttnBwdLaunch {
-  const void* q;
-  const void* k;
-  const void* v;
-  const void* o;
-  const void* dout;
-  int64_t qsb, qss, qsh, ksb, kss, ksh, vsb, vss, vsh, osb, oss, osh, dsb, dss, dsh;
-  void* dq;     // strided outputs: dq [B,Sq,H,64], dk / dv [B,Sk,H,64]
-  void* dk;
-  void* dv;
-  int64_t dqsb, dqss, dqsh, dksb, dkss, dksh, dvsb, dvss, dvsh;
-  const float* lse;  // [B][H][lse_stride]
-  float* D;          // workspace [B][H][lse_stride], [2][B][H][lse_stride] with a key mask
-  int lse_stride;    // attn_lse_stride(Sq)
-  int B, H;
-  int Sq, Sk;        // as in AttnLaunch; dQ runs ceil(Sq/128) tiles, dK/dV ceil(Sk/128)
-  float scale, dropout;
-  uint32_t seed;
-  bool causal;
-  DType dtype;
-  const float* kbias = nullptr;  // the forward's prepared key mask, or both null
-  const unsigned char* klive = nullptr;
+// backward, two launches and no atomics: the dQ kernel first (ceil(Sq/128) tiles), which
+// also writes D = rowsum(dO*O) and, under a key mask, the guarded copy of lse behind it;
+// then the dK/dV kernel (ceil(Sk/128) tiles).  No preprocess launch.
+struct AttnBwd {
+  AttnView o, dout;      // inputs shaped like q
+  AttnView dq, dk, dv;   // strided outputs: dq like q, dk / dv like k
+  const float* lse;      // [B][H][attn_lse_stride(Sq)]
+  float* D;              // workspace shaped like lse, [2] of them with a key mask
 };
-void attn_bwd(const AttnBwdLaunch& L, hipStream_t st);
+void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 
 // ---- fused softmax cross entropy with label smoothing (xentropy.hip) ---------
 // x [rows, V] row-major (T = fp32/fp16/bf16); loss [rows] (TO), lse [rows] fp32

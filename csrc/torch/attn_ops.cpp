@@ -8,29 +8,31 @@
 namespace amd {
 
 namespace {
-void check_view(const at::Tensor& t, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(3) == 64, "attn: ", what,
-              " must be a [B,S,H,64] GPU tensor");
-  TORCH_CHECK(t.stride(3) == 1, "attn: ", what, ": head dim must be contiguous");
-  TORCH_CHECK(((uintptr_t)t.data_ptr() % 16) == 0 && t.stride(0) % 8 == 0 &&
-                  t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0,
-              "attn: ", what, ": 16-byte aligned rows required");
-  // the kernels' tile DMA uses 32-bit per-lane row offsets (csrc/hip/attention.hip)
-  TORCH_CHECK(t.stride(1) >= 0 && t.stride(1) < (int64_t{1} << 24), "attn: ", what,
-              ": sequence stride must be below 2^24 elements");
-}
-
+// the alignment the kernels need of a 4-d 16-bit tensor: contiguous, 16-byte aligned rows
 bool view_ok(const at::Tensor& t) {
   return t.stride(3) == 1 && ((uintptr_t)t.data_ptr() % 16) == 0 && t.stride(0) % 8 == 0 &&
          t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0;
 }
 
+// the kernels' view of a [B,S,H,64] tensor, or the reason it has none
+AttnView view_of(const at::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(3) == 64, "attn: ", what,
+              " must be a [B,S,H,64] GPU tensor");
+  TORCH_CHECK(t.stride(3) == 1, "attn: ", what, ": head dim must be contiguous");
+  TORCH_CHECK(view_ok(t), "attn: ", what, ": 16-byte aligned rows required");
+  // the kernels' tile DMA uses 32-bit per-lane row offsets (csrc/hip/attention.hip)
+  TORCH_CHECK(t.stride(1) >= 0 && t.stride(1) < (int64_t{1} << 24), "attn: ", what,
+              ": sequence stride must be below 2^24 elements");
+  return {t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)};
+}
+
 // q [B, Sq, H, 64], k / v [B, Sk, H, 64]: one B, H and dtype, any strides
-AttnLaunch make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                       bool causal, double dropout, int64_t seed, double scale) {
-  check_view(q, "q");
-  check_view(k, "k");
-  check_view(v, "v");
+AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                        bool causal, double dropout, int64_t seed, double scale) {
+  AttnProblem L;
+  L.q = view_of(q, "q");
+  L.k = view_of(k, "k");
+  L.v = view_of(v, "v");
   TORCH_CHECK(v.sizes() == k.sizes(), "attn: k and v shapes differ: ", k.sizes(), " and ",
               v.sizes());
   TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2),
@@ -45,16 +47,9 @@ AttnLaunch make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tenso
               "attn: causal is defined for equal query and key lengths only, got Sq = ",
               q.size(1), ", Sk = ", k.size(1));
   TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "attn: dropout must be in [0, 1)");
-  AttnLaunch L;
-  L.q = q.data_ptr(); L.k = k.data_ptr(); L.v = v.data_ptr();
-  L.qsb = q.stride(0); L.qss = q.stride(1); L.qsh = q.stride(2);
-  L.ksb = k.stride(0); L.kss = k.stride(1); L.ksh = k.stride(2);
-  L.vsb = v.stride(0); L.vss = v.stride(1); L.vsh = v.stride(2);
   L.B = (int)q.size(0); L.Sq = (int)q.size(1); L.Sk = (int)k.size(1); L.H = (int)q.size(2);
   L.scale = (float)scale; L.dropout = (float)dropout; L.seed = (uint32_t)seed;
   L.causal = causal; L.dtype = dtype_of(q);
-  L.lse_stride = attn_lse_stride(L.Sq);
-  L.o = nullptr; L.lse = nullptr;
   return L;
 }
 
@@ -121,19 +116,18 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
                                                double scale, c10::optional<at::Tensor> key_bias,
                                                c10::optional<at::Tensor> key_live) {
   c10::NoGradGuard no_grad_;
-  AttnLaunch L = make_launch(q, k, v, causal, dropout, seed, scale);
+  AttnProblem L = make_launch(q, k, v, causal, dropout, seed, scale);
   check_key_mask(key_bias, key_live, q, L.B, L.Sk, &L.kbias, &L.klive);
+  const int Sp = attn_lse_stride(L.Sq);
   at::Tensor o = at::empty({L.B, L.Sq, L.H, 64}, q.options());
-  at::Tensor lse = at::empty({L.B, L.H, L.lse_stride}, q.options().dtype(at::kFloat));
-  L.o = o.data_ptr();
-  L.lse = lse.data_ptr<float>();
+  at::Tensor lse = at::empty({L.B, L.H, Sp}, q.options().dtype(at::kFloat));
   if (L.Sk == 0) {  // no key to attend to: o = 0, lse = log2(0), no launch
     o.zero_();
     lse.fill_(-std::numeric_limits<float>::infinity());
   } else if (L.Sq > 0 && L.B * L.H > 0) {
-    attn_fwd(L, cur_stream());
+    attn_fwd(L, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
   }
-  return {o, L.lse_stride == L.Sq ? lse : lse.narrow(2, 0, L.Sq)};
+  return {o, Sp == L.Sq ? lse : lse.narrow(2, 0, L.Sq)};
 }
 
 void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
@@ -141,15 +135,16 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
                  at::Tensor dq, at::Tensor dk, at::Tensor dv, c10::optional<at::Tensor> key_bias,
                  c10::optional<at::Tensor> key_live) {
   c10::NoGradGuard no_grad_;
-  AttnLaunch F = make_launch(q, k, v, causal, dropout, seed, scale);
+  AttnProblem F = make_launch(q, k, v, causal, dropout, seed, scale);
   check_key_mask(key_bias, key_live, q, F.B, F.Sk, &F.kbias, &F.klive);
   if (!(dout.dim() == 4 && view_ok(dout))) dout = dout.contiguous();
   if (!(o.dim() == 4 && view_ok(o))) o = o.contiguous();
-  check_view(dout, "dout");
-  check_view(o, "o");
-  check_view(dq, "dq");
-  check_view(dk, "dk");
-  check_view(dv, "dv");
+  AttnBwd G;
+  G.dout = view_of(dout, "dout");
+  G.o = view_of(o, "o");
+  G.dq = view_of(dq, "dq");
+  G.dk = view_of(dk, "dk");
+  G.dv = view_of(dv, "dv");
   for (const at::Tensor* t : {&dout, &o, &dq}) {
     TORCH_CHECK(t->sizes() == q.sizes(), "attn bwd: shape mismatch: o, dout and dq must be "
                 "shaped like q ", q.sizes(), ", got ", t->sizes());
@@ -162,7 +157,7 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   }
   for (const at::Tensor* t : {&dout, &o, &dq, &dk, &dv})
     TORCH_CHECK(t->device() == q.device(), "attn bwd: every tensor must be on q's device");
-  const int B = F.B, H = F.H, S = F.Sq, Sp = F.lse_stride;
+  const int B = F.B, H = F.H, S = F.Sq, Sp = attn_lse_stride(F.Sq);
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.dim() == 3 && lse.size(0) == B &&
                   lse.size(1) == H && lse.size(2) == S && lse.device() == q.device(),
               "attn bwd: lse must be fp32 [B, H, Sq] on q's device");
@@ -184,23 +179,9 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
     dv.zero_();
     return;
   }
-  AttnBwdLaunch L;
-  L.q = F.q; L.k = F.k; L.v = F.v; L.o = o.data_ptr(); L.dout = dout.data_ptr();
-  L.qsb = F.qsb; L.qss = F.qss; L.qsh = F.qsh;
-  L.ksb = F.ksb; L.kss = F.kss; L.ksh = F.ksh;
-  L.vsb = F.vsb; L.vss = F.vss; L.vsh = F.vsh;
-  L.osb = o.stride(0); L.oss = o.stride(1); L.osh = o.stride(2);
-  L.dsb = dout.stride(0); L.dss = dout.stride(1); L.dsh = dout.stride(2);
-  L.dq = dq.data_ptr(); L.dk = dk.data_ptr(); L.dv = dv.data_ptr();
-  L.dqsb = dq.stride(0); L.dqss = dq.stride(1); L.dqsh = dq.stride(2);
-  L.dksb = dk.stride(0); L.dkss = dk.stride(1); L.dksh = dk.stride(2);
-  L.dvsb = dv.stride(0); L.dvss = dv.stride(1); L.dvsh = dv.stride(2);
-  L.lse = lse.data_ptr<float>(); L.D = D.data_ptr<float>(); L.lse_stride = Sp;
-  L.B = B; L.H = H; L.Sq = S; L.Sk = F.Sk;
-  L.scale = F.scale; L.dropout = F.dropout; L.seed = F.seed;
-  L.causal = causal; L.dtype = F.dtype;
-  L.kbias = F.kbias; L.klive = F.klive;
-  attn_bwd(L, cur_stream());
+  G.lse = lse.data_ptr<float>();
+  G.D = D.data_ptr<float>();
+  attn_bwd(F, G, cur_stream());
 }
 
 }  // namespace amd

@@ -7,68 +7,16 @@ new arguments, the routing of EncdecMultiheadAttn, and argument validation.
 References and bounds are those of tests/test_attention_gpu.py and
 tests/test_attention_mask_gpu.py: o rtol = atol = 2e-2, lse 1e-3, gradients max-error /
 max-reference below 2e-2 (bf16) / 6e-3 (fp16), 3e-2 with dropout."""
-import math
-
 import pytest
 import torch
-import torch.nn.functional as F
+
+from attn_ref import (DEV, NEG, _C, close as _close, finite as _finite,
+                      mask_kwargs as _mask_kwargs, no_sdpa as _no_sdpa, ref_attention,
+                      ref_grads as _ref_grads)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-NEG = float("-inf")
 DTYPES = [torch.bfloat16, torch.float16]
-
-
-def _C():
-    from apex_example_amd import _native
-
-    return _native.require().attn
-
-
-# ------------------------------------------------------------------ reference
-def ref_attention(q, k, v, bias=None, p=0.0, seed=0):
-    """fp32 reference on q [B, Sq, H, D], k / v [B, Sk, H, D] and an additive [B, Sk] key
-    bias -> (o [B, Sq, H, D], lse [B, H, Sq] log2, dead [B, H, Sq]: rows with no live key)."""
-    B, Sq, H, D = q.shape
-    Sk = k.size(1)
-    qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
-    s = qf @ kf.transpose(-1, -2) / math.sqrt(D)
-    if bias is not None:
-        s = s + bias.float().view(B, 1, 1, Sk)
-    dead = (s == NEG).all(-1, keepdim=True)
-    lse = torch.logsumexp(s, -1) / math.log(2.0)
-    pr = torch.softmax(torch.where(dead, torch.zeros_like(s), s), -1)
-    pr = torch.where(dead, torch.zeros_like(pr), pr)  # fully masked rows: p = 0, finite grads
-    if p > 0:
-        import dropout_hash
-
-        t = dropout_hash.thr8(p)
-        keep = dropout_hash.hash_bytes(B, H, Sq, seed, SK=Sk, device=q.device) >= t
-        pr = pr * keep * (256.0 / (256 - t))
-    return (pr @ vf).permute(0, 2, 1, 3), lse, dead.squeeze(-1)
-
-
-def _ref_grads(q, k, v, do, bias=None, p=0.0, seed=0):
-    qf, kf, vf = (t.detach().float().clone().requires_grad_(True) for t in (q, k, v))
-    o, _, _ = ref_attention(qf, kf, vf, bias, p=p, seed=seed)
-    o.backward(do.float())
-    return qf.grad, kf.grad, vf.grad
-
-
-def _close(a, b, rel, what="", floor=0.0):
-    """max |a - b| / max |b| < rel.  ``floor``: a lower limit of the denominator, for a
-    reference that is identically zero (see test_cross_fwd_bwd)."""
-    err = (a.float() - b).abs().max().item()
-    scale = max(b.abs().max().item(), floor) + 1e-6
-    print("%s max err %.3e / max magnitude %.3e = %.3e (bound %.1e)" % (
-        what, err, scale, err / scale, rel))
-    assert err / scale < rel, (what, err, scale)
-
-
-def _finite(*ts):
-    for t in ts:
-        assert torch.isfinite(t.float()).all()
 
 
 def _rel(dt):
@@ -195,6 +143,40 @@ def test_cross_strided_module_layout(B, Sq, Sk, H, dt):
     assert torch.equal(kv2.grad, results[1][2].view(Sk, B, 2, H, 64).permute(1, 0, 2, 3, 4))
 
 
+def test_gradient_layouts_per_entry_point():
+    """The layout of the gradients each entry point hands to autograd, seen by hooks on
+    sequence-first views (a leaf's .grad is re-laid out by autograd itself): packed inputs
+    and the q beside a packed kv get a gradient of their own strides (torch.empty_like),
+    separate q, k, v dense-contiguous ones."""
+    from apex_example_amd.ops import fused_attention, fused_attention_kv, fused_attention_qkv
+
+    B, Sq, Sk, H, dt = 1, 65, 64, 1, torch.bfloat16
+    torch.manual_seed(2)
+    q = torch.randn(Sq, B, H, 64, device=DEV, dtype=dt, requires_grad=True).transpose(0, 1)
+    kv = torch.randn(Sk, B, 2, H, 64, device=DEV, dtype=dt, requires_grad=True).permute(
+        1, 0, 2, 3, 4)
+    qkv = torch.randn(Sq, B, 3, H, 64, device=DEV, dtype=dt, requires_grad=True).permute(
+        1, 0, 2, 3, 4)
+    k, v = kv.unbind(2)
+    do = torch.randn(B, Sq, H, 64, device=DEV, dtype=dt)
+    assert q.stride() == (64, 64, 64, 1) and kv.stride() == (128, 128, 64, 64, 1)
+    assert qkv.stride() == (192, 192, 64, 64, 1)
+
+    def layouts(o, *ts):
+        seen = {}
+        hooks = [t.register_hook(lambda g, i=i: seen.__setitem__(i, g.stride()))
+                 for i, t in enumerate(ts)]
+        o.backward(do)
+        for h in hooks:
+            h.remove()
+        return [seen[i] for i in range(len(ts))]
+
+    assert layouts(fused_attention_kv(q, kv), q, kv) == [q.stride(), kv.stride()]
+    assert layouts(fused_attention(q, k, v), q, k, v) == [
+        (Sq * H * 64, H * 64, 64, 1), (Sk * H * 64, H * 64, 64, 1), (Sk * H * 64, H * 64, 64, 1)]
+    assert layouts(fused_attention_qkv(qkv), qkv) == [qkv.stride()]
+
+
 # ------------------------------------------------------------- 3. key masks
 MASK_SHAPES = [(3, 100, 200, 2), (2, 200, 100, 2)]
 MASK_FORMS = ["right", "left", "additive", "allmasked"]
@@ -222,12 +204,6 @@ def make_bias(form, B, Sk):
     return torch.zeros(B, Sk).masked_fill(m, NEG), True
 
 
-def _mask_kwargs(bias, boolean):
-    if boolean:
-        return {"key_padding_mask": (bias == NEG).to(DEV)}
-    return {"key_bias": bias.to(DEV)}
-
-
 _MASKED = {}
 
 
@@ -242,8 +218,8 @@ def _masked_case(B, Sq, Sk, H, dt, form):
         prep = _C().prepare_key_mask((bias == NEG).to(DEV) if boolean else bias.to(DEV), Sk)
         _, lse = _C().fwd(q, k, v, False, 0.0, 0, 0.125, *prep)
         bd = bias.to(DEV)
-        ro, rlse, dead = ref_attention(q, k, v, bd)
-        rq, rk, rv = _ref_grads(q, k, v, do, bd)
+        ro, rlse, dead = ref_attention(q, k, v, bias=bd)
+        rq, rk, rv = _ref_grads(q, k, v, do, bias=bd)
         _MASKED[key] = dict(bias=bias, q=q, k=k, v=v, do=do, kw=kw, o=o, lse=lse, dq=dq, dk=dk,
                             dv=dv, ro=ro, rlse=rlse, dead=dead, rq=rq, rk=rk, rv=rv)
     return _MASKED[key]
@@ -312,8 +288,8 @@ def _dropout_case(B, Sq, Sk, H, lens=None):
         prep = (pm.bias, pm.live)
     o = FusedAttentionFunction.apply(q, k, v, False, p, 0.125, seed, *prep)
     o.backward(do)
-    ro, _, _ = ref_attention(q.detach(), k.detach(), v.detach(), bias, p=p, seed=seed)
-    rq, rk, rv = _ref_grads(q, k, v, do, bias, p=p, seed=seed)
+    ro, _, _ = ref_attention(q.detach(), k.detach(), v.detach(), bias=bias, p=p, seed=seed)
+    rq, rk, rv = _ref_grads(q, k, v, do, bias=bias, p=p, seed=seed)
     _finite(o, q.grad, k.grad, v.grad)
     torch.testing.assert_close(o.detach().float(), ro, rtol=3e-2, atol=3e-2)
     _close(q.grad, rq, 3e-2, "dq")
@@ -380,13 +356,6 @@ def test_equal_lengths_kv_path_matches_qkv(p, masked):
 
 
 # ---------------------------------------------------------------- 7. routing
-def _no_sdpa(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("F.scaled_dot_product_attention was called")
-
-    monkeypatch.setattr(F, "scaled_dot_product_attention", boom)
-
-
 def _encdec_pair(**kw):
     from apex_example_amd.contrib.multihead_attn import EncdecMultiheadAttn
 
@@ -451,7 +420,7 @@ def test_attention_bshd_unequal_lengths_all_mask_forms(monkeypatch):
     _no_sdpa(monkeypatch)
     o = attention_bshd(q, k, v, 0.0)
     torch.testing.assert_close(o.float(), ref_attention(q, k, v)[0], rtol=2e-2, atol=2e-2)
-    ro = ref_attention(q, k, v, add)[0]
+    ro = ref_attention(q, k, v, bias=add)[0]
     for kpm, additive in ((gone, False), (add, True), (prepare_key_mask(gone), False)):
         o = attention_bshd(q, k, v, 0.0, kpm, None, additive)
         torch.testing.assert_close(o.float(), ro, rtol=2e-2, atol=2e-2)

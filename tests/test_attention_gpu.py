@@ -1,61 +1,12 @@
 """Fused attention kernels (csrc/hip/attention.hip) vs fp32 torch references,
 including the exact counter-hash dropout masks."""
-import math
-
 import pytest
 import torch
-import torch.nn.functional as F
+
+from attn_ref import DEV, _C, close as _close, ref_attention, ref_grads as _ref_grads
+from dropout_hash import keep_mask
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-M32 = 0xFFFFFFFF
-
-
-def _C():
-    from apex_example_amd import _native
-
-    return _native.require().attn
-
-
-def _mul32(a, c):
-    return (a * c) & M32
-
-
-def _murmur32(x):
-    x = x ^ (x >> 16)
-    x = _mul32(x, 0x7FEB352D)
-    x = x ^ (x >> 15)
-    x = _mul32(x, 0x846CA68B)
-    return x ^ (x >> 16)
-
-
-def _umul24(x, c):
-    return ((x & 0xFFFFFF) * (c & 0xFFFFFF)) & M32
-
-
-def drop_keep_mask(B, H, S, seed, p, device="cpu"):
-    """[B, H, S(q), S(k)] keep mask of the kernels' hash (int64 torch arithmetic):
-    drop_mix(drop_base(seed, bh) + q * kDropQ + (key >> 2) * kDropK), byte (key & 3)
-    against round(256 p) (csrc/hip/attention.hip)."""
-    from dropout_hash import keep_mask
-    return keep_mask(B, H, S, seed, p, device=device)
-
-
-def ref_attention(q, k, v, causal, p=0.0, seed=0):
-    """fp32 reference on [B, S, H, D] inputs -> ([B, S, H, D], lse [B, H, S] log2)."""
-    B, S, H, D = q.shape
-    qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
-    s = qf @ kf.transpose(-1, -2) / math.sqrt(D)
-    if causal:
-        s = s.masked_fill(torch.ones(S, S, device=q.device).triu(1).bool(), float("-inf"))
-    lse = torch.logsumexp(s, -1) / math.log(2.0)
-    pr = torch.softmax(s, -1)
-    if p > 0:
-        # the mask mirror runs where the scores are (production shapes: 134 M entries)
-        keep, scale = drop_keep_mask(B, H, S, seed, p, device=q.device)
-        pr = pr * keep * scale
-    return (pr @ vf).permute(0, 2, 1, 3), lse
 
 
 def _qkv(B, S, H, dt, fused=True):
@@ -72,7 +23,7 @@ def _qkv(B, S, H, dt, fused=True):
 def test_attn_fwd(B, S, H, causal, dt):
     q, k, v = _qkv(B, S, H, dt)
     o, lse = _C().fwd(q, k, v, causal, 0.0, 0, 1.0 / 8.0)
-    ro, rlse = ref_attention(q, k, v, causal)
+    ro, rlse, _ = ref_attention(q, k, v, causal)
     torch.testing.assert_close(o.float(), ro, rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(lse, rlse, rtol=1e-3, atol=1e-3)
 
@@ -81,26 +32,13 @@ def test_attn_fwd(B, S, H, causal, dt):
 def test_attn_fwd_dropout_exact_mask(causal):
     q, k, v = _qkv(2, 256, 2, torch.bfloat16, fused=False)
     o, _ = _C().fwd(q, k, v, causal, 0.1, 1234, 1.0 / 8.0)
-    ro, _ = ref_attention(q, k, v, causal, p=0.1, seed=1234)
+    ro, _, _ = ref_attention(q, k, v, causal, p=0.1, seed=1234)
     torch.testing.assert_close(o.float(), ro, rtol=3e-2, atol=3e-2)
-    keep, _ = drop_keep_mask(2, 2, 256, 1234, 0.1)
+    keep, _ = keep_mask(2, 2, 256, 1234, 0.1)
     assert abs(1 - keep.float().mean().item() - 0.1) < 0.01
 
 
 # ------------------------------------------------------------------ backward
-def _ref_grads(q, k, v, do, causal, p=0.0, seed=0):
-    qf, kf, vf = (t.detach().float().clone().requires_grad_(True) for t in (q, k, v))
-    o, _ = ref_attention(qf, kf, vf, causal, p=p, seed=seed)
-    o.backward(do.float())
-    return qf.grad, kf.grad, vf.grad
-
-
-def _close(a, b, rel):
-    err = (a.float() - b).abs().max().item()
-    scale = b.abs().max().item() + 1e-6
-    assert err / scale < rel, (err, scale)
-
-
 @pytest.mark.parametrize("B,S,H", [(2, 128, 2), (1, 200, 3), (2, 512, 2), (1, 64, 1)])
 @pytest.mark.parametrize("causal", [False, True])
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
@@ -209,7 +147,7 @@ def test_attn_production_gpt2_causal_s1024():
     q, k, v = (torch.randn(B, S, H, 64, device=DEV, dtype=torch.float16).requires_grad_(True)
                for _ in range(3))
     o = fused_attention(q, k, v, causal=True)
-    ro, _ = ref_attention(q.detach(), k.detach(), v.detach(), True)
+    ro, _, _ = ref_attention(q.detach(), k.detach(), v.detach(), True)
     _close(o.detach(), ro, 1e-2)
     do = torch.randn_like(o)
     o.backward(do)
@@ -227,7 +165,7 @@ def test_attn_production_bert_dropout_s512():
     qkv = torch.randn(B, S, 3, H, 64, device=DEV, dtype=torch.bfloat16, requires_grad=True)
     o = FusedQKVAttentionFunction.apply(qkv, False, 0.1, 0.125, 777)
     q, k, v = qkv.detach().unbind(2)
-    ro, _ = ref_attention(q, k, v, False, p=0.1, seed=777)
+    ro, _, _ = ref_attention(q, k, v, False, p=0.1, seed=777)
     _close(o.detach(), ro, 3e-2)
     do = torch.randn_like(o)
     o.backward(do)

@@ -6,12 +6,12 @@ import math
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+from attn_ref import (DEV, NEG, close as _close, finite as _finite, mask_kwargs as _mask_kwargs,
+                      no_sdpa as _no_sdpa, ref_attention, ref_grads as _ref_grads)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-NEG = float("-inf")
 SHAPES = [(1, 64, 1), (6, 200, 2), (4, 320, 2)]
 PATTERNS = ["right", "left", "hole", "bernoulli", "additive", "allmasked", "mixed"]
 
@@ -64,57 +64,9 @@ def make_bias(pattern, B, S):
     return torch.zeros(B, S).masked_fill(m, NEG), True
 
 
-# ------------------------------------------------------------------ reference
-def ref_attention(q, k, v, causal, bias=None, p=0.0, seed=0):
-    """fp32 reference on [B, S, H, D] inputs and an additive [B, S] key bias ->
-    ([B, S, H, D], lse [B, H, S] log2, dead [B, H, S]: rows with no live key)."""
-    B, S, H, D = q.shape
-    qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
-    s = qf @ kf.transpose(-1, -2) / math.sqrt(D)
-    if bias is not None:
-        s = s + bias.float().view(B, 1, 1, S)
-    if causal:
-        s = s.masked_fill(torch.ones(S, S, device=q.device).triu(1).bool(), NEG)
-    dead = (s == NEG).all(-1, keepdim=True)
-    lse = torch.logsumexp(s, -1) / math.log(2.0)
-    pr = torch.softmax(torch.where(dead, torch.zeros_like(s), s), -1)
-    pr = torch.where(dead, torch.zeros_like(pr), pr)  # fully masked rows: p = 0, finite grads
-    if p > 0:
-        from dropout_hash import keep_mask
-
-        keep, scale = keep_mask(B, H, S, seed, p, device=q.device)
-        pr = pr * keep * scale
-    return (pr @ vf).permute(0, 2, 1, 3), lse, dead.squeeze(-1)
-
-
-def _ref_grads(q, k, v, do, causal, bias, p=0.0, seed=0):
-    qf, kf, vf = (t.detach().float().clone().requires_grad_(True) for t in (q, k, v))
-    o, _, _ = ref_attention(qf, kf, vf, causal, bias, p=p, seed=seed)
-    o.backward(do.float())
-    return qf.grad, kf.grad, vf.grad
-
-
-def _close(a, b, rel):
-    err = (a.float() - b).abs().max().item()
-    scale = b.abs().max().item() + 1e-6
-    print("max err %.3e / max magnitude %.3e = %.3e (bound %.1e)" % (err, scale, err / scale, rel))
-    assert err / scale < rel, (err, scale)
-
-
-def _finite(*ts):
-    for t in ts:
-        assert torch.isfinite(t.float()).all()
-
-
 def _packed(B, S, H, dt, seed=0):
     torch.manual_seed(seed)
     return torch.randn(B, S, 3, H, 64, device=DEV, dtype=dt)
-
-
-def _mask_kwargs(bias, boolean):
-    if boolean:
-        return {"key_padding_mask": (bias == NEG).to(DEV)}
-    return {"key_bias": bias.to(DEV)}
 
 
 _CASES = {}
@@ -364,13 +316,6 @@ def test_prepared_mask_is_reusable():
 
 
 # -------------------------------------------------------------------- routing
-def _no_sdpa(monkeypatch):
-    def boom(*a, **k):
-        raise AssertionError("F.scaled_dot_product_attention was called")
-
-    monkeypatch.setattr(F, "scaled_dot_product_attention", boom)
-
-
 def _mha_pair(**kw):
     from apex_example_amd.contrib.multihead_attn import SelfMultiheadAttn
 
