@@ -139,6 +139,10 @@ class Bottleneck(nn.Module):
         out = self.bn2(self.conv2(out))
         if proj is not None and fuse_ds:
             return bn_add_bn_relu(self.bn3.bn, self.conv3(out), self.downsample.bn.bn, proj)
+        if self.downsample is None and self.bn3.fused and isinstance(self.conv3, Conv2d1x1):
+            # identity block: bn3's passes recompute conv3 where that is cheaper than reading
+            # its output (layers 1-2; ops/conv.py forward_bn3)
+            return self.bn3(self.conv3.forward_bn3(out, identity), identity)
         return self.bn3(self.conv3(out), identity)
 
 

@@ -68,6 +68,37 @@ class BnBwdSrc:
         self.result = None
 
 
+class ConvRec:
+    """How to recompute this BN's input x = conv1x1(a, w) (ops/conv.py forward_bn3: an
+    identity bottleneck's conv3 with at most 128 input channels, whose input is a quarter of
+    x's bytes).  ``applied``: the conv call already wrote x together with this BN's
+    y = relu(bn(x) + z) and ReLU mask from one kernel (conv.conv1x1_bn_apply) - the BN
+    forward takes them instead of launching its apply pass, which would read x again.
+    ``bwd``: the elementwise backward recomputes x instead of reading it
+    (conv.conv1x1_bn_bwd).  Both are bitwise the separate passes; x itself is always
+    written, so a BN that cannot use the record just ignores it.  The conv output carries
+    the record as ``_amd_bn_rec``."""
+    __slots__ = ("a", "w", "bwd", "applied")
+
+    def __init__(self, a, w, bwd):
+        self.a, self.w, self.bwd = a, w, bwd
+        self.applied = None   # (z, gamma, beta, y, mask), consumed once
+
+    def take_applied(self, z, weight, bias):
+        """(y, mask) if they were formed from exactly these tensors, else None."""
+        ent, self.applied = self.applied, None
+        if ent is None or z is None or weight is None or bias is None:
+            return None
+        if (ent[0].data_ptr() != z.data_ptr() or ent[0].shape != z.shape
+                or ent[1] is not weight or ent[2] is not bias):
+            return None
+        return ent[3], ent[4]
+
+
+REC_FWD_CALLS = [0]  # BN forwards / backwards that recomputed their input (tests)
+REC_BWD_CALLS = [0]
+
+
 def _bwd_src(x, xl, mean, invstd, weight, bias, mask, fuse_relu, has_z):
     if not (_BWD_EPI and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
             and x is xl and x.size(1) % 64 == 0
@@ -270,6 +301,8 @@ class BatchNormFunction(torch.autograd.Function):
         # on a single GPU (DistributedDataParallel has the same switch)
         collective = world > 1 or bool(force_collectives)
         want_mask = bool(fuse_relu) and zl is not None and xl.is_cuda
+        rec, _TLS.rec = getattr(_TLS, "rec", None), None
+        ctx.rec = None
         if not collective and xl.is_cuda:
             if slab is not None:
                 # statistics already summed by the producing conv's epilogue
@@ -277,7 +310,14 @@ class BatchNormFunction(torch.autograd.Function):
                 mean_g, invstd = C.slab_train_stats(slab, count, slab_shift, running_mean,
                                                     running_var, num_batches_tracked,
                                                     float(eps), float(momentum))
-                if want_mask:
+                done = (rec.take_applied(zl, weight, bias)
+                        if rec is not None and want_mask and x is xl else None)
+                if done is not None:
+                    # y and the ReLU mask came out of the kernel that wrote x (from the same
+                    # slab's mean / invstd): no apply pass, no read of x
+                    REC_FWD_CALLS[0] += 1
+                    y, mask = done
+                elif want_mask:
                     y, mask = C.apply_mask(xl, mean_g, invstd, weight, bias, zl, bool(fuse_relu))
                 else:
                     y, mask = C.apply(xl, mean_g, invstd, weight, bias, zl, bool(fuse_relu)), None
@@ -299,6 +339,8 @@ class BatchNormFunction(torch.autograd.Function):
             zg = getattr(z, "grad_fn", None) if z is not None else None
             ctx.zctx = zg if isinstance(zg, BatchNormFunction._backward_cls) else None
             ctx.pre = None
+            if rec is not None and rec.bwd and x is xl and weight is not None:
+                ctx.rec = rec
             ctx.orig_shape, ctx.has_z, ctx.shape_channel_last = orig_shape, z is not None, \
                 shape_channel_last
             return y.view(orig_shape) if shape_channel_last else y
@@ -434,8 +476,15 @@ class BatchNormFunction(torch.autograd.Function):
                     zc.pre = (dyl.data_ptr(), dyl._version, s1, s2, gw2, gb2)
                     return (dx, dyl, gw if need_w else None, gb if need_w else None, None, None,
                             None, None, None, None, None, None, None, None, None)
-            dx, _ = C.backward_elemt(dyl, xl, mean, invstd, weight, bias, sum_dy, sum_dy_xmu,
-                                     total, None, False, False)
+            rec, ctx.rec = ctx.rec, None
+            if rec is not None and ctx.world == 1:
+                # the same elementwise pass with x recomputed from the conv's input
+                REC_BWD_CALLS[0] += 1
+                dx = _native.require().conv.conv1x1_bn_bwd(
+                    rec.a, rec.w, dyl, mean, invstd, weight, sum_dy, sum_dy_xmu, total)
+            else:
+                dx, _ = C.backward_elemt(dyl, xl, mean, invstd, weight, bias, sum_dy,
+                                         sum_dy_xmu, total, None, False, False)
             return (dx, dyl if ctx.has_z else None, gw if need_w else None,
                     gb if need_w else None, None, None, None, None, None, None, None, None, None,
                     None, None)
@@ -522,12 +571,15 @@ def take_slab(x, bn):
 
 def batch_norm_act(x, weight, bias, running_mean, running_var, training, momentum, eps,
                    z=None, fuse_relu=False, process_group=False, shape_channel_last=False,
-                   num_batches_tracked=None, force_collectives=False, slab=None, slab_shift=None):
+                   num_batches_tracked=None, force_collectives=False, slab=None, slab_shift=None,
+                   rec=None):
     """Functional fused BN(+z)(+ReLU).  ``process_group=False`` -> local statistics.
     ``num_batches_tracked`` (int64 tensor) is incremented on the device.  ``slab``:
-    per-tile statistics a producing conv already summed ([C][2][S], ops/conv.py)."""
+    per-tile statistics a producing conv already summed ([C][2][S], ops/conv.py).
+    ``rec``: the ConvRec of x (handed to the autograd node through the thread-local)."""
     if training:
         _TLS.src = None
+        _TLS.rec = rec
         y = BatchNormFunction.apply(x, z, weight, bias, running_mean, running_var, eps, momentum,
                                     process_group, fuse_relu, shape_channel_last,
                                     num_batches_tracked, force_collectives, slab, slab_shift)
@@ -565,6 +617,7 @@ class BatchNorm2dReLU(torch.nn.BatchNorm2d):
 
     def forward(self, x, z=None):
         slab, shift = take_slab(x, self)
+        rec = x.__dict__.pop("_amd_bn_rec", None) if isinstance(x, torch.Tensor) else None
         if not x.is_cuda and not _native.available():
             y = super().forward(x)
             if z is not None:
@@ -584,7 +637,7 @@ class BatchNorm2dReLU(torch.nn.BatchNorm2d):
                               self.running_var if self.track_running_stats else None,
                               use_batch, momentum, self.eps, z=z, fuse_relu=self.fuse_relu,
                               process_group=False, num_batches_tracked=nbt,
-                              slab=slab if use_batch else None, slab_shift=shift)
+                              slab=slab if use_batch else None, slab_shift=shift, rec=rec)
 
 
 # ---------------------------------------------------------------- relu(bn3(x) + bn_d(xd))

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 from .. import _native
 from . import _ddp_direct
-from .batch_norm import bn_src_of
+from .batch_norm import BatchNorm2dReLU, ConvRec, bn_src_of
 
 # Weight gradients on a side stream (APEX_AMD_WGRAD_STREAM=0 disables; a documented
 # debugging switch, docs/KNOBS.md): the data
@@ -464,9 +464,76 @@ def _dgrad_bn(dy, wprep, add, src, add_stride2=False):
     return g
 
 
+# ---------------------------------------------------------------- conv3 recomputed in
+# bn3's passes.  An identity bottleneck's conv3 at layers 1-2 (64 -> 256 @ 56, 128 -> 512
+# @ 28) reads a quarter of the bytes it writes, and bn3's apply and elementwise-backward
+# passes - HBM-bound - each read that output x3 again.  With a ConvRec on x3
+# (ops/batch_norm.py) the passes run as epilogues of the conv's own launch on its input
+# (csrc/hip/conv_igemm.hip conv_tap_k EPI 3 / 4) and read the 4x smaller tensor instead:
+#   forward:  conv3 launches statistics-only (EPI 2), mean / invstd are finalized from that
+#             slab, then ONE kernel writes x3, y = relu(bn3(x3) + z) and the mask - all
+#             inside the conv call, so x3 is complete when it returns (hooks on bn3 see
+#             its real input); the BN forward finalizes the slab as always (the running
+#             statistics, the same mean / invstd) and takes y and the mask as they are;
+#   backward: dx3 = k1 g + k2 x3 + k3 with x3 recomputed (the sums still come from the
+#             consuming conv1's dgrad epilogue; off that branch the plain kernels run on
+#             the stored x3).
+# Every tensor is bitwise the separate passes' (tests/test_bn3_recompute_gpu.py).
+# _BN3_RECOMPUTE = False keeps the separate passes; _REC_FWD / _REC_BWD hold the (Cin, Cout)
+# shapes where each form measured faster (tools/diag/bn3_recompute_bench.py, docs/PERF.md).
+#   us per call, bs 256:    conv+stats + apply  ->  stats-only + fused   |  backward
+#   64 -> 256 @ 56          167.5 + 245.0 = 412.5 -> 101.5 + 250.6 = 352.1 | 237.8 -> 168.7
+#   128 -> 512 @ 28          83.2 + 120.1 = 203.3 ->  65.5 + 153.8 = 219.3 | 118.2 -> 107.9
+# so the 28x28 forward keeps the separate passes.
+_BN3_RECOMPUTE = True
+_REC_FWD = {(64, 256)}
+_REC_BWD = {(64, 256), (128, 512)}
+
+
+def _recompute_plan(conv, x, z):
+    """(ConvRec, the BN whose forward pass is fused too or None) for ``bn3(conv(x), z)``
+    where the recompute forms apply, else (None, None)."""
+    ci, co = conv.in_channels, conv.out_channels
+    fwd, bwd = (ci, co) in _REC_FWD, (ci, co) in _REC_BWD
+    if not (_BN3_RECOMPUTE and (fwd or bwd) and conv._gemm_ok(x) and x.dtype == torch.bfloat16
+            and ci % 64 == 0 and ci <= 128 and co % 128 == 0 and _native.available()):
+        return None, None
+    bn = _stats_bn(conv, x)
+    n, _, h, w = x.shape
+    if not (type(bn) is BatchNorm2dReLU and bn.fuse_relu and bn.affine
+            and bn.track_running_stats and bn.momentum is not None
+            and bn.weight.dtype == torch.float32 and bn.bias.dtype == torch.float32
+            and bn.weight.is_contiguous() and bn.bias.is_contiguous()
+            and _shift_of(bn) is not None and bn.running_var.dtype == torch.float32
+            and isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.bfloat16
+            and tuple(z.shape) == (n, co, h, w)
+            and z.is_contiguous(memory_format=torch.channels_last)
+            and z.data_ptr() % 16 == 0):
+        return None, None
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return None, None
+    if not _native.require().conv.recompute_1x1_ok(n * h * w, ci, co):
+        return None, None
+    return ConvRec(x.detach(), conv.weight.detach(), bwd), bn if fwd else None
+
+
+def _apply_now(rec, bn, x3, z):
+    """Fill x3 = conv(rec.a, rec.w) and form bn's y and ReLU mask from the same tiles; the
+    batch mean / invstd come from x3's slab (no side effect: bn's forward finalizes it
+    again with the running statistics)."""
+    C = _native.require()
+    slab, shift, _ = x3._amd_bn_stats
+    count = x3.numel() // x3.size(1)
+    mean, invstd = C.bn.slab_train_stats(slab, count, shift, None, None, None, float(bn.eps),
+                                         0.0)
+    y, mask = C.conv.conv1x1_bn_apply(rec.a, rec.w, x3, mean, invstd, bn.weight, bn.bias, z)
+    rec.applied = (z, bn.weight, bn.bias, y, mask)
+
+
 class Conv1x1GemmFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bn=None, src=None):
+    def forward(ctx, x, weight, bn=None, src=None, stats_only=False):
         ctx.save_for_backward(x, weight)
         ctx.src = src
         if ctx.needs_input_grad[1]:
@@ -475,6 +542,12 @@ class Conv1x1GemmFunction(torch.autograd.Function):
         if ctx.needs_input_grad[0] and weight.dtype == torch.bfloat16 and (
                 src is not None or _own_1x1(x.dtype, weight.shape[0], ci, n * h * w)):
             _register_prep(weight)  # its dgrad runs on the own kernel with W^T
+        if stats_only:
+            # y is allocated and left UNWRITTEN: forward_bn3 fills it before it returns
+            shift = _shift_of(bn)
+            y, slab = _native.require().conv.conv1x1_stats_only(x, weight, shift)
+            _TLS.slab = (slab, shift, bn)
+            return y
         return _conv1x1_fwd(x, weight, bn)
 
     @staticmethod
@@ -499,7 +572,7 @@ class Conv1x1GemmFunction(torch.autograd.Function):
             else:
                 so, sa = _side_out(side, weight)
                 dw = side.run(lambda: _wgrad_1x1_w(dy, x, weight, so, sa), dy, x)
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
 class Conv1x1SkipFunction(torch.autograd.Function):
@@ -720,6 +793,20 @@ class Conv2d1x1(nn.Conv2d):
             return _tag_stats(Conv1x1Stride2Function.apply(x, self.weight, _stats_bn(self, x)))
         return F.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation,
                         self.groups)
+
+    def forward_bn3(self, x, z):
+        """conv(x) feeding ``relu(bn3(conv(x)) + z)``: where conv3 is cheaper to recompute
+        than its output is to read, the output carries a ConvRec for the BN (with that
+        BN's y and ReLU mask already formed where the forward form applies)."""
+        rec, bn = _recompute_plan(self, x, z)
+        if rec is None:
+            return self.forward(x)
+        y = _tag_stats(Conv1x1GemmFunction.apply(x, self.weight, _stats_bn(self, x),
+                                                 bn_src_of(x), bn is not None))
+        if bn is not None:
+            _apply_now(rec, bn, y, z)
+        y._amd_bn_rec = rec
+        return y
 
     def forward_with_skip(self, x):
         """(conv(x), x) with the residual-gradient add fused into the dgrad GEMM."""

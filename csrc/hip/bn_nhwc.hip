@@ -292,11 +292,14 @@ __global__ void __launch_bounds__(kBNThreads)
       uint32_t mb = 0;
 #pragma unroll
       for (int i = 0; i < W; ++i) {
-        float o = fmaf(v[u][i], sc[i], sh[i]);
+        float o;
         if constexpr (ZA) {
+          o = fmaf(v[u][i], sc[i], sh[i]);
           o += to_f32(from_f32<T>(fmaf(zz[u][i], scz[i], shz[i])));
         } else if constexpr (ZZ) {
-          o += zz[u][i];
+          o = bn_apply_z(v[u][i], sc[i], sh[i], zz[u][i]);
+        } else {
+          o = fmaf(v[u][i], sc[i], sh[i]);
         }
         mb |= (o > 0.f ? 1u : 0u) << i;
         v[u][i] = relu ? fmaxf(o, 0.f) : o;
@@ -414,12 +417,8 @@ __global__ void __launch_bounds__(kBNThreads)
   stage_params(C, cb, ctile * W, [&](int c, int k) {
     const float wc = wload(w, c, 1.f);
     chan_affine(mean, invstd, wc, wload(b, c, 0.f), c, s_par[0][k], s_par[1][k]);
-    const float is = invstd[c];
-    const float mdy = sum_dy[c] * inv_n, mdyx = sum_dy_xmu[c] * inv_n;
-    const float q1 = is * wc, q2 = -is * is * is * wc * mdyx;
-    s_par[2][k] = q1;
-    s_par[3][k] = q2;
-    s_par[4][k] = -is * wc * mdy - q2 * mean[c];
+    bn_bwd_consts(invstd[c], wc, mean[c], sum_dy[c], sum_dy_xmu[c], inv_n, s_par[2][k],
+                  s_par[3][k], s_par[4][k]);
     if constexpr (X2) s_par[X2 ? 5 : 0][k] = mean2[c];
   });
   float t1[W], t2[W], m2[W];
@@ -469,7 +468,7 @@ __global__ void __launch_bounds__(kBNThreads)
           d = o > 0.f ? d : 0.f;
         }
         dv[u][i] = d;
-        xv[u][i] = fmaf(d, k1[i], fmaf(xv[u][i], k2[i], k3[i]));
+        xv[u][i] = bn_bwd_elem(d, xv[u][i], k1[i], k2[i], k3[i]);
         if constexpr (X2) {
           t1[i] += d;
           t2[i] = fmaf(d, x2v[u][i] - m2[i], t2[i]);

@@ -28,6 +28,7 @@
 
 #include "amd_dev.h"
 #include "amd_kernels.h"
+#include "bn_common.h"
 
 namespace amd {
 
@@ -318,6 +319,119 @@ __device__ __forceinline__ void bnbwd_store(const bf16_t* T, bf16_t* __restrict_
   }
 }
 
+// Recompute epilogues (conv_tap_k EPI == 3 / 4, dense 1x1 forward launches only): the conv
+// output tile x3 is the INPUT of a BatchNorm whose elementwise pass runs here on the bf16
+// tile in LDS instead of re-reading x3 from memory (K <= 128: the K loop's operand is a
+// quarter of x3's bytes or less).
+//   EPI 3: stores x3 and y = relu(x3 * sc + sh + z) with its ReLU bitmask (apply_k ZZ);
+//   EPI 4: stores dx = g * k1 + x3 * k2 + k3 (backward_k RM 0), x3 itself is not stored.
+// The arithmetic is bn_common.h's, on exactly the bf16 values the plain launch stores, so
+// both are bitwise the separate pass.  rec_prefetch is bnbwd_prefetch's scheme: the row
+// loads (z or g) and the raw channel constants go out before the accumulators are written
+// to LDS and are waited for once, in rec_store.
+template <int BM, int BN, int CT = kCT>
+struct RecPre {
+  static constexpr int CPR = BN / 8;
+  static constexpr int RGS = CT / CPR;
+  static constexpr int ROWS = BM / RGS;
+  uint4 av[ROWS];
+  float mu[8], iv[8], wv[8], bv[8], sd[8], sx[8];
+};
+
+template <int EPI, int BM, int BN, int CT>
+__device__ __forceinline__ void rec_prefetch(const ConvGeom& g, const ConvBnEpi& ep, int m0,
+                                             int n0, RecPre<BM, BN, CT>& P) {
+  using PT = RecPre<BM, BN, CT>;
+  const int tid = threadIdx.x;
+  const int cc = tid % PT::CPR, rg = tid / PT::CPR;
+  const int c0 = n0 + cc * 8;
+  const float* zf = reinterpret_cast<const float*>(g_zero16);
+  {
+    const float* wp = ep.w ? ep.w + c0 : g_one8;
+    const float* bp = ep.b ? ep.b + c0 : zf;
+    const float* mp = ep.mean + c0;
+    const float* ip = ep.invstd + c0;
+    const float* dp = EPI == 4 ? ep.sum_dy + c0 : zf;
+    const float* xp = EPI == 4 ? ep.sum_dy_xmu + c0 : zf;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      P.mu[i] = mp[i];
+      P.iv[i] = ip[i];
+      P.wv[i] = wp[i];
+      P.bv[i] = bp[i];
+      P.sd[i] = dp[i];
+      P.sx[i] = xp[i];
+    }
+  }
+  const bf16_t* addp = static_cast<const bf16_t*>(ep.add);
+#pragma unroll
+  for (int q = 0; q < PT::ROWS; ++q) {
+    const int m = m0 + q * PT::RGS + rg;
+    const int mm = m < g.M ? m : 0;  // rows past M load row 0 and are never stored
+    P.av[q] = *reinterpret_cast<const uint4*>(addp + (int64_t)mm * g.NC + c0);
+  }
+}
+
+template <int EPI, int BM, int BN, int CT, int TS>
+__device__ __forceinline__ void rec_store(const bf16_t* T, bf16_t* __restrict__ y,
+                                          const ConvGeom& g, const ConvBnEpi& ep, int m0, int n0,
+                                          const RecPre<BM, BN, CT>& P) {
+  using PT = RecPre<BM, BN, CT>;
+  const int tid = threadIdx.x;
+  const int cc = tid % PT::CPR, rg = tid / PT::CPR;
+  const int c0 = n0 + cc * 8;
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the prefetch has landed (bnbwd_store_t)
+  float k1[8], k2[8], k3[8];  // EPI 3: k1 = sc, k2 = sh
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if constexpr (EPI == 3) {
+      chan_affine(P.mu, P.iv, P.wv[i], P.bv[i], i, k1[i], k2[i]);
+      k3[i] = 0.f;
+    } else {
+      bn_bwd_consts(P.iv[i], P.wv[i], P.mu[i], P.sd[i], P.sx[i], ep.inv_n, k1[i], k2[i], k3[i]);
+    }
+  }
+  bf16_t* y2 = static_cast<bf16_t*>(ep.out2);
+#pragma unroll
+  for (int q = 0; q < PT::ROWS; ++q) {
+    const int row = q * PT::RGS + rg;
+    const int m = m0 + row;
+    if (m >= g.M) continue;
+    const uint4 tv = *reinterpret_cast<const uint4*>(T + row * TS + cc * 8);
+    const int64_t off = (int64_t)m * g.NC + c0;
+    if constexpr (EPI == 3) *reinterpret_cast<uint4*>(y + off) = tv;
+    const unsigned tw[4] = {tv.x, tv.y, tv.z, tv.w};
+    const unsigned aw[4] = {P.av[q].x, P.av[q].y, P.av[q].z, P.av[q].w};
+    unsigned ow[4], mb = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float xx[2] = {__uint_as_float(tw[k] << 16), __uint_as_float(tw[k] & 0xffff0000u)};
+      const float aa[2] = {__uint_as_float(aw[k] << 16), __uint_as_float(aw[k] & 0xffff0000u)};
+      unsigned short hb[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int i = 2 * k + h;
+        float r;
+        if constexpr (EPI == 3) {
+          const float o = bn_apply_z(xx[h], k1[i], k2[i], aa[h]);
+          mb |= (o > 0.f ? 1u : 0u) << i;
+          r = fmaxf(o, 0.f);
+        } else {
+          r = bn_bwd_elem(aa[h], xx[h], k1[i], k2[i], k3[i]);
+        }
+        hb[h] = __builtin_bit_cast(unsigned short, (bf16_t)r);
+      }
+      ow[k] = (unsigned)hb[0] | ((unsigned)hb[1] << 16);
+    }
+    if constexpr (EPI == 3) {
+      *reinterpret_cast<uint4*>(y2 + off) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+      ep.rmask_out[(int64_t)m * (g.NC >> 3) + (c0 >> 3)] = (uint8_t)mb;
+    } else {
+      *reinterpret_cast<uint4*>(y + off) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    }
+  }
+}
+
 // NB = 1 (no DMA ring): for 1x1 convs with one or two K-tiles (K = 64 / 128: the
 // ResNet layer1-2 channel-expanding convs) - nothing to overlap inside a workgroup, so
 // the LDS goes to more resident workgroups instead (3 per CU: one's loads overlap
@@ -328,7 +442,7 @@ __device__ __forceinline__ void bnbwd_store(const bf16_t* T, bf16_t* __restrict_
 template <int MODE, int BM, int BN, int WM, int WN, int NB, int EPI = 0, int CT = kCT,
           int BK = kBK, bool EARLY = false>
 __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
-                                          ? 1 : (NB == 1 && EPI == 0 ? 3 : 2))
+                                          ? 1 : (NB == 1 && (EPI == 0 || EPI == 2) ? 3 : 2))
     conv_tap_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wt,
                bf16_t* __restrict__ y, ConvGeom g, float* __restrict__ slab,
                const float* __restrict__ shift, ConvBnEpi ep) {
@@ -442,13 +556,16 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
   // loaded now so the latency hides under the K loop
   constexpr int CPR = BN / 8;  // 16-byte chunks per output row
   // EPI == 1 (BN-backward epilogue, ConvBnEpi): slab gets sum(g), sum(g * (x - mean))
-  const bool want_stats = EPI == 1 ? slab != nullptr
+  // EPI == 2: EPI 0 without the output stores (the statistics only); EPI 3 / 4: the
+  // recompute epilogues (rec_store), no statistics
+  constexpr bool plain = EPI == 0 || EPI == 2;
+  const bool want_stats = EPI >= 3 ? false : EPI == 1 ? slab != nullptr
                                    : (MODE == kFwd3 || MODE == kFwd1) && slab != nullptr;
   const int scc = tid % CPR;
   float shv[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
-    shv[i] = (EPI == 0 && want_stats && shift) ? shift[n0 + scc * 8 + i] : 0.f;
+    shv[i] = (plain && want_stats && shift) ? shift[n0 + scc * 8 + i] : 0.f;
 
   // BN-backward epilogue operands (EPI == 1): issued after the K loop - issued earlier
   // they would sit at the head of the in-order vmcnt queue and every counted wait of the
@@ -456,6 +573,7 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
   // consumed after barriers that wait for LDS only, so they fly under the accumulator ->
   // LDS tile write instead of being waited for at a __syncthreads()
   BnPre<BM, BN, CT> pre;
+  RecPre<BM, BN, CT> rpre;
   if constexpr (EPI == 1 && EARLY) bnbwd_prefetch<MODE, BM, BN, CT>(g, ep, m0, n0, z, pre);
 
   {
@@ -507,6 +625,10 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
   if constexpr (EPI == 1) {
     if constexpr (!EARLY) bnbwd_prefetch<MODE, BM, BN, CT>(g, ep, m0, n0, z, pre);
     lds_barrier();
+  } else if constexpr (EPI >= 3) {
+    static_assert(EPI < 3 || MODE == kFwd1, "recompute epilogues: dense 1x1 forward only");
+    rec_prefetch<EPI, BM, BN, CT>(g, ep, m0, n0, rpre);
+    lds_barrier();
   } else {
     __syncthreads();
   }
@@ -528,7 +650,7 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
                           ((unsigned)__builtin_bit_cast(unsigned short, (bf16_t)acc[i][j][3]) << 16);
       *reinterpret_cast<uint2*>(T + row * TS + col) = make_uint2(lo, hi);
     }
-  if constexpr (EPI == 1) {
+  if constexpr (EPI == 1 || EPI >= 3) {
     lds_barrier();
   } else {
     __syncthreads();
@@ -546,6 +668,8 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
   for (int i = 0; i < 8; ++i) s1[i] = s2[i] = 0.f;
   if constexpr (EPI == 1) {
     bnbwd_store<MODE, BM, BN, CT, TS>(T, y, g, ep, m0, n0, z, pre, s1, s2);
+  } else if constexpr (EPI >= 3) {
+    rec_store<EPI, BM, BN, CT, TS>(T, y, g, ep, m0, n0, rpre);
   } else
   for (int c = tid; c < BM * CPR; c += CT) {
     const int row = c / CPR, cc = c - row * CPR;
@@ -559,7 +683,7 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
       opix = (int64_t)(n * g.YH + gh * g.ys + (z >> 1)) * g.YW + gw * g.ys + (z & 1);
     }
     const uint4 v = *reinterpret_cast<const uint4*>(T + row * TS + cc * 8);
-    *reinterpret_cast<uint4*>(y + opix * g.NC + n0 + cc * 8) = v;
+    if constexpr (EPI != 2) *reinterpret_cast<uint4*>(y + opix * g.NC + n0 + cc * 8) = v;
     if (want_stats) {
       const unsigned wv[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -649,16 +773,22 @@ void launch_conv_tap(const bf16_t* a, const bf16_t* w, bf16_t* y, const ConvGeom
   if (g.M == 0) return;
   const int nclasses = MODE == kDgrad3 || MODE == kDgrad1 ? 4 : 1;
   constexpr bool k1 = MODE == kFwd1 || MODE == kDgrad1;
-  if (EPI == 1 && MODE == kFwd1 && g.NC % 128 == 0 && g.M >= 50176 && g.KC < 256) {
-    const dim3 grid = conv_grid((g.M + 63) / 64, g.NC / 128, nclasses, k1);
-    // K <= 128 (two to four 32-deep K-tiles): the epilogue's loads go out at kernel start
-    // and fly under the K loop's DMA (64 -> 256 @ 56 +skip: 324 -> 307 us, 128 -> 512
-    // @ 28: 176 -> 171; at K = 256 the held registers cost a wave per SIMD: 110 -> 115)
-    if (g_bnbwd_early && g.KC <= 128)
-      hipLaunchKernelGGL((conv_tap_k<MODE, 64, 128, 2, 2, 3, EPI, kCT, 32, true>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-    else
-      hipLaunchKernelGGL((conv_tap_k<MODE, 64, 128, 2, 2, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-  } else if (MODE == kFwd1 && g.NC % 128 == 0 && g.KC / kBK <= 1) {
+  // (EPI 2 - 4, the stats-only and recompute forms of a 1x1 forward, take EPI 0's plan:
+  // their results must be bitwise the plain launch's)
+  if constexpr (EPI == 1 && MODE == kFwd1) {
+    if (g.NC % 128 == 0 && g.M >= 50176 && g.KC < 256) {
+      const dim3 grid = conv_grid((g.M + 63) / 64, g.NC / 128, nclasses, k1);
+      // K <= 128 (two to four 32-deep K-tiles): the epilogue's loads go out at kernel start
+      // and fly under the K loop's DMA (64 -> 256 @ 56 +skip: 324 -> 307 us, 128 -> 512
+      // @ 28: 176 -> 171; at K = 256 the held registers cost a wave per SIMD: 110 -> 115)
+      if (g_bnbwd_early && g.KC <= 128)
+        hipLaunchKernelGGL((conv_tap_k<MODE, 64, 128, 2, 2, 3, EPI, kCT, 32, true>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
+      else
+        hipLaunchKernelGGL((conv_tap_k<MODE, 64, 128, 2, 2, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
+      return;
+    }
+  }
+  if (MODE == kFwd1 && g.NC % 128 == 0 && g.KC / kBK <= 1) {
     const dim3 grid = conv_grid((g.M + kBM - 1) / kBM, g.NC / 128, nclasses, k1);
     hipLaunchKernelGGL((conv_tap_k<MODE, 128, 128, 2, 2, 1, EPI>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
   } else if (g.NC % 128 == 0) {
@@ -667,9 +797,11 @@ void launch_conv_tap(const bf16_t* a, const bf16_t* w, bf16_t* y, const ConvGeom
       hipLaunchKernelGGL((conv_tap_k<MODE, 128, 128, 2, 2, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
     else
       hipLaunchKernelGGL((conv_tap_k<MODE, 128, 128, 2, 2, 2, EPI>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-  } else {
+  } else if constexpr (EPI < 2) {
     const dim3 grid = conv_grid((g.M + kBM - 1) / kBM, g.NC / 64, nclasses, k1);
     hipLaunchKernelGGL((conv_tap_k<MODE, 128, 64, 4, 1, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
+  } else {
+    std::abort();  // conv1x1_recompute_ok: 128-wide output tiles only
   }
 }
 
@@ -2030,6 +2162,31 @@ void conv_nhwc_fwd(const void* x, const void* w, void* y, int N, int H, int W, i
     launch_conv3h<0>(xp, wp, yp, g, N, st, stats_slab, stats_shift, ConvBnEpi{});
   else if (ksize == 3) launch_conv_tap<kFwd3>(xp, wp, yp, g, st, stats_slab, stats_shift);
   else launch_conv_tap<kFwd1>(xp, wp, yp, g, st, stats_slab, stats_shift);
+}
+
+// The stats-only and recompute forms of a stride-1 1x1 forward (amd_kernels.h): the shapes
+// conv_nhwc_fwd runs on conv_tap_k's 128-wide tiles with at most two 64-channel K-tiles
+bool conv1x1_recompute_ok(int64_t M, int Cin, int Cout) {
+  return Cin % 64 == 0 && Cin <= 128 && Cout % 128 == 0 && M > 0 && M < ((int64_t)1 << 31) &&
+         !conv1x1_g4w(M, Cin, Cout, 1);
+}
+void conv1x1_stats_only(const void* x, const void* w, int N, int H, int W, int Cin, int Cout,
+                        float* slab, const float* shift, hipStream_t st) {
+  const ConvGeom g{H, W, H, W, 1, H, W, 1, Cin, Cout, N * H * W, Cin};
+  launch_conv_tap<kFwd1, 2>(static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w), nullptr,
+                            g, st, slab, shift);
+}
+void conv1x1_bn_apply(const void* x, const void* w, void* x3, int N, int H, int W, int Cin,
+                      int Cout, const ConvBnEpi& ep, hipStream_t st) {
+  const ConvGeom g{H, W, H, W, 1, H, W, 1, Cin, Cout, N * H * W, Cin};
+  launch_conv_tap<kFwd1, 3>(static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w),
+                            static_cast<bf16_t*>(x3), g, st, nullptr, nullptr, ep);
+}
+void conv1x1_bn_bwd(const void* x, const void* w, void* dx, int N, int H, int W, int Cin,
+                    int Cout, const ConvBnEpi& ep, hipStream_t st) {
+  const ConvGeom g{H, W, H, W, 1, H, W, 1, Cin, Cout, N * H * W, Cin};
+  launch_conv_tap<kFwd1, 4>(static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(w),
+                            static_cast<bf16_t*>(dx), g, st, nullptr, nullptr, ep);
 }
 
 int conv_bnbwd_mtiles(int N, int H, int W, int Cout, int ksize, int Cin) {

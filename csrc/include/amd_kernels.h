@@ -369,10 +369,33 @@ struct ConvBnEpi {
   int relu_mode;
   int add_s2;            // 1: `add` is COMPACT [N][H/2][W/2][C] and lands on the even
                          // (h, w) pixels only (a stride-2 1x1 downsample's input gradient)
+  // the recompute epilogues only (conv1x1_bn_apply / conv1x1_bn_bwd below; `add` is then
+  // the residual z, resp. the gradient g)
+  void* out2;            // apply: y = relu(bn(x3) + z), bf16 [M][C]
+  uint8_t* rmask_out;    // apply: the 1-bit ReLU mask [M][C/8]
+  const float* sum_dy;      // backward: [C]
+  const float* sum_dy_xmu;  // backward: [C]
+  float inv_n;              // backward: 1 / rows
 };
 void conv_nhwc_fwd_bnbwd(const void* dy, const void* w, void* g, int N, int H, int W, int Cin,
                          int Cout, int ksize, int stride, const ConvBnEpi& ep, float* slab,
                          hipStream_t st);
+// A stride-1 1x1 conv with K <= 128 (ResNet's layer-1/2 conv3) is cheaper to run again
+// than its 4x wider output is to read: three forms of conv_nhwc_fwd's own launch for such
+// a conv, same tile plan, tile order and K loop, so every value is bitwise conv_nhwc_fwd's.
+//   stats_only: the statistics slab of conv_nhwc_fwd, no output stores;
+//   bn_apply:   stores x3 = conv(x) and, from the same tile, y = relu(bn(x3) + z) with the
+//               ReLU bitmask (ep.add = z, ep.out2 = y, ep.rmask_out, mean / invstd / w / b) -
+//               bitwise nhwc_apply on x3;
+//   bn_bwd:     stores dx = k1 * g + k2 * x3 + k3 (ep.add = g, ep.sum_dy / sum_dy_xmu /
+//               inv_n) - bitwise nhwc_backward without ReLU; x3 is not written.
+bool conv1x1_recompute_ok(int64_t M, int Cin, int Cout);
+void conv1x1_stats_only(const void* x, const void* w, int N, int H, int W, int Cin, int Cout,
+                        float* slab, const float* shift, hipStream_t st);
+void conv1x1_bn_apply(const void* x, const void* w, void* x3, int N, int H, int W, int Cin,
+                      int Cout, const ConvBnEpi& ep, hipStream_t st);
+void conv1x1_bn_bwd(const void* x, const void* w, void* dx, int N, int H, int W, int Cin,
+                    int Cout, const ConvBnEpi& ep, hipStream_t st);
 // BatchNorm statistics from such a slab: local training mode (mean, invstd, running
 // stats, num_batches_tracked) or SyncBN's packed [mean | biased var | count]
 // (slab is channel-major [2][C][S]: one launch, no workspace)

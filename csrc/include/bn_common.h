@@ -33,6 +33,29 @@ __device__ __forceinline__ void chan_affine(const float* mean, const float* invs
   sh = b - mean[c] * sc;
 }
 
+// The elementwise passes' arithmetic, shared with the conv epilogues that recompute the BN
+// input instead of reading it (conv_igemm.hip, EPI 3 / 4): one definition, so a fused
+// result is bitwise the separate pass's.
+//   forward with a residual: o = x*sc + sh + z (the caller rounds relu(o) to the tensor type)
+__device__ __forceinline__ float bn_apply_z(float x, float sc, float sh, float z) {
+  float o = fmaf(x, sc, sh);
+  o += z;
+  return o;
+}
+//   backward: dx = dy*k1 + x*k2 + k3 with the per-channel constants of bn_bwd_consts
+__device__ __forceinline__ float bn_bwd_elem(float dy, float x, float k1, float k2, float k3) {
+  return fmaf(dy, k1, fmaf(x, k2, k3));
+}
+__device__ __forceinline__ void bn_bwd_consts(float is, float wc, float mu, float sum_dy,
+                                              float sum_dy_xmu, float inv_n, float& q1,
+                                              float& q2, float& q3) {
+  const float mdy = sum_dy * inv_n, mdyx = sum_dy_xmu * inv_n;
+  const float a = is * wc, b = -is * is * is * wc * mdyx;
+  q1 = a;
+  q2 = b;
+  q3 = -is * wc * mdy - b * mu;
+}
+
 template <typename TW>
 __device__ __forceinline__ float wload(const TW* p, int c, float dflt) {
   return p ? to_f32(p[c]) : dflt;

@@ -154,6 +154,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("add_stride2") = false);
   conv.def("conv_fwd_stats", &conv_nhwc_fwd_stats_op, py::arg("x"), py::arg("w"),
            py::arg("stride") = 1, py::arg("shift") = py::none());
+  conv.def("recompute_1x1_ok", &conv1x1_recompute_ok_op, py::arg("M"), py::arg("Cin"),
+           py::arg("Cout"));
+  conv.def("conv1x1_stats_only", &conv1x1_stats_only_op, py::arg("x"), py::arg("w"),
+           py::arg("shift") = py::none());
+  conv.def("conv1x1_bn_apply", &conv1x1_bn_apply_op, py::arg("x"), py::arg("w"), py::arg("x3"),
+           py::arg("mean"), py::arg("invstd"), py::arg("bn_weight"), py::arg("bn_bias"),
+           py::arg("z"));
+  conv.def("conv1x1_bn_bwd", &conv1x1_bn_bwd_op, py::arg("x"), py::arg("w"), py::arg("g"),
+           py::arg("mean"), py::arg("invstd"), py::arg("bn_weight"), py::arg("sum_dy"),
+           py::arg("sum_dy_xmu"), py::arg("count"));
   conv.def("conv_dgrad_s2", &conv_nhwc_dgrad_s2_op);
   conv.def("conv_dgrad_s2_bnbwd", &conv_nhwc_dgrad_s2_bnbwd_op, py::arg("dy"), py::arg("wt"),
            py::arg("H"), py::arg("W"), py::arg("x"), py::arg("rmask"), py::arg("mean"),

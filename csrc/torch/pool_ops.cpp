@@ -168,6 +168,104 @@ std::tuple<at::Tensor, at::Tensor> conv_nhwc_fwd_stats_op(at::Tensor x, at::Tens
   return {y, slab};
 }
 
+// ---- stride-1 1x1 conv with K <= 128 recomputed inside its BatchNorm's passes ----------
+namespace {
+struct Rec1x1 {
+  int64_t N, Cin, H, W, Cout;
+};
+Rec1x1 rec1x1_check(at::Tensor& x, at::Tensor& w, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && w.dim() == 4 && w.is_cuda(), what,
+              ": 4-D GPU tensors expected");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, what,
+              ": bf16 only");
+  Rec1x1 r{x.size(0), x.size(1), x.size(2), x.size(3), w.size(0)};
+  TORCH_CHECK(w.size(1) == r.Cin && w.size(2) == 1 && w.size(3) == 1, what, ": 1x1 weight");
+  TORCH_CHECK(conv1x1_recompute_ok(r.N * r.H * r.W, (int)r.Cin, (int)r.Cout), what,
+              ": needs Cin 64 | 128, Cout % 128 == 0 and the own-kernel route");
+  x = x.contiguous(at::MemoryFormat::ChannelsLast);
+  w = w.contiguous(at::MemoryFormat::ChannelsLast);
+  return r;
+}
+const float* rec_vec(const at::Tensor& t, int64_t C, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == C,
+              "conv1x1 recompute: ", what, " must be a contiguous fp32 [C] GPU tensor");
+  return t.data_ptr<float>();
+}
+void rec_like_out(const at::Tensor& t, const Rec1x1& r, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(0) == r.N && t.size(1) == r.Cout &&
+                  t.size(2) == r.H && t.size(3) == r.W && t.scalar_type() == at::kBFloat16 &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  (uintptr_t)t.data_ptr() % 16 == 0,
+              "conv1x1 recompute: ", what,
+              " must be a channels-last bf16 tensor shaped like the conv output");
+}
+}  // namespace
+
+bool conv1x1_recompute_ok_op(int64_t M, int64_t Cin, int64_t Cout) {
+  return conv1x1_recompute_ok(M, (int)Cin, (int)Cout);
+}
+
+// (x3 UNWRITTEN, slab): conv_fwd_stats without the output stores; conv1x1_bn_apply fills x3
+std::tuple<at::Tensor, at::Tensor> conv1x1_stats_only_op(at::Tensor x, at::Tensor w,
+                                                         c10::optional<at::Tensor> shift) {
+  c10::NoGradGuard no_grad_;
+  const Rec1x1 r = rec1x1_check(x, w, "conv1x1_stats_only");
+  const float* sp = nullptr;
+  if (shift.has_value() && shift->defined()) sp = rec_vec(*shift, r.Cout, "shift");
+  at::Tensor y = at::empty({r.N, r.Cout, r.H, r.W},
+                           x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  const int S = conv_fwd_mtiles((int)r.N, (int)r.H, (int)r.W, (int)r.Cout, 1, 1, (int)r.Cin);
+  at::Tensor slab = at::empty({2, r.Cout, S}, x.options().dtype(at::kFloat));
+  conv1x1_stats_only(x.data_ptr(), w.data_ptr(), (int)r.N, (int)r.H, (int)r.W, (int)r.Cin,
+                     (int)r.Cout, slab.data_ptr<float>(), sp, cur_stream());
+  return {y, slab};
+}
+
+// writes x3 = conv(x, w) INTO the given tensor and returns (y, mask) = bn.apply_mask(x3, ...)
+std::tuple<at::Tensor, at::Tensor> conv1x1_bn_apply_op(at::Tensor x, at::Tensor w, at::Tensor x3,
+                                                       at::Tensor mean, at::Tensor invstd,
+                                                       at::Tensor bn_w, at::Tensor bn_b,
+                                                       at::Tensor z) {
+  c10::NoGradGuard no_grad_;
+  const Rec1x1 r = rec1x1_check(x, w, "conv1x1_bn_apply");
+  rec_like_out(x3, r, "x3");
+  rec_like_out(z, r, "z");
+  ConvBnEpi ep{};
+  ep.mean = rec_vec(mean, r.Cout, "mean");
+  ep.invstd = rec_vec(invstd, r.Cout, "invstd");
+  ep.w = rec_vec(bn_w, r.Cout, "weight");
+  ep.b = rec_vec(bn_b, r.Cout, "bias");
+  ep.add = z.data_ptr();
+  at::Tensor y = at::empty_like(x3);
+  at::Tensor mask = at::empty({r.N * r.H * r.W, r.Cout / 8}, x.options().dtype(at::kByte));
+  ep.out2 = y.data_ptr();
+  ep.rmask_out = mask.data_ptr<uint8_t>();
+  conv1x1_bn_apply(x.data_ptr(), w.data_ptr(), x3.data_ptr(), (int)r.N, (int)r.H, (int)r.W,
+                   (int)r.Cin, (int)r.Cout, ep, cur_stream());
+  return {y, mask};
+}
+
+// dx = bn.backward_elemt(g, conv(x, w), ...) without ReLU / residual, x3 recomputed
+at::Tensor conv1x1_bn_bwd_op(at::Tensor x, at::Tensor w, at::Tensor g, at::Tensor mean,
+                             at::Tensor invstd, at::Tensor bn_w, at::Tensor sum_dy,
+                             at::Tensor sum_dy_xmu, double count) {
+  c10::NoGradGuard no_grad_;
+  const Rec1x1 r = rec1x1_check(x, w, "conv1x1_bn_bwd");
+  rec_like_out(g, r, "g");
+  ConvBnEpi ep{};
+  ep.mean = rec_vec(mean, r.Cout, "mean");
+  ep.invstd = rec_vec(invstd, r.Cout, "invstd");
+  ep.w = rec_vec(bn_w, r.Cout, "weight");
+  ep.sum_dy = rec_vec(sum_dy, r.Cout, "sum_dy");
+  ep.sum_dy_xmu = rec_vec(sum_dy_xmu, r.Cout, "sum_dy_xmu");
+  ep.inv_n = (float)(1.0 / count);
+  ep.add = g.data_ptr();
+  at::Tensor dx = at::empty_like(g);
+  conv1x1_bn_bwd(x.data_ptr(), w.data_ptr(), dx.data_ptr(), (int)r.N, (int)r.H, (int)r.W,
+                 (int)r.Cin, (int)r.Cout, ep, cur_stream());
+  return dx;
+}
+
 // Stride-1 data-gradient conv (dy with the rotated 3x3 / transposed 1x1 filter) whose
 // output is the gradient of a BN(+ReLU) output: stores g = relu_mask * (conv + add) and
 // returns it with that BN's per-M-tile backward sums [2][C][S] (ConvBnEpi).

@@ -29,6 +29,17 @@ std::tuple<at::Tensor, at::Tensor> conv_nhwc_fwd_bnbwd_op(
     c10::optional<at::Tensor> rmask, at::Tensor mean, at::Tensor invstd,
     c10::optional<at::Tensor> bn_w, c10::optional<at::Tensor> bn_b, int64_t relu_mode,
     bool add_stride2 = false);
+// a stride-1 1x1 conv with K <= 128 recomputed inside its BatchNorm's elementwise passes
+bool conv1x1_recompute_ok_op(int64_t M, int64_t Cin, int64_t Cout);
+std::tuple<at::Tensor, at::Tensor> conv1x1_stats_only_op(at::Tensor x, at::Tensor w,
+                                                         c10::optional<at::Tensor> shift);
+std::tuple<at::Tensor, at::Tensor> conv1x1_bn_apply_op(at::Tensor x, at::Tensor w, at::Tensor x3,
+                                                       at::Tensor mean, at::Tensor invstd,
+                                                       at::Tensor bn_w, at::Tensor bn_b,
+                                                       at::Tensor z);
+at::Tensor conv1x1_bn_bwd_op(at::Tensor x, at::Tensor w, at::Tensor g, at::Tensor mean,
+                             at::Tensor invstd, at::Tensor bn_w, at::Tensor sum_dy,
+                             at::Tensor sum_dy_xmu, double count);
 at::Tensor conv_nhwc_dgrad_s2_op(at::Tensor dy, at::Tensor wt, int64_t H, int64_t W);
 at::Tensor conv_nhwc_wgrad_op(at::Tensor dy, at::Tensor x, at::ScalarType out_dtype, int64_t algo,
                               int64_t stride, int64_t ksize, c10::optional<at::Tensor> out, bool accumulate = true);
