@@ -575,7 +575,7 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training, momentu
                    rec=None):
     """Functional fused BN(+z)(+ReLU).  ``process_group=False`` -> local statistics.
     ``num_batches_tracked`` (int64 tensor) is incremented on the device.  ``slab``:
-    per-tile statistics a producing conv already summed ([C][2][S], ops/conv.py).
+    per-tile statistics a producing conv already summed ([2][C][S], ops/conv.py).
     ``rec``: the ConvRec of x (handed to the autograd node through the thread-local)."""
     if training:
         _TLS.src = None

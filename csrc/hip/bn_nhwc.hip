@@ -36,6 +36,9 @@ NGeom ngeom(int64_t C, bool vec) {
   if (g.ctile < 1) g.ctile = 1;
   g.rows_iter = kBNThreads / g.ctile;
   g.cblocks = (int)((cv + g.ctile - 1) / g.ctile);
+  // C < 8 asked for the vector geometry (bn_stats_workspace sizes for both): cv = 0 gave
+  // cblocks = 0 and reduce_splits divided by it (SIGFPE on any channels-last C < 8)
+  if (g.cblocks < 1) g.cblocks = 1;
   return g;
 }
 
