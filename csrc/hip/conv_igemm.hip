@@ -746,7 +746,7 @@ __global__ void __launch_bounds__(CT, (NB * (BM + BN) * BK * 2 > 80 * 1024)
 //  * 64-wide output tiles: 32-deep K-tiles on a 3-deep ring (layer-1 3x3 64@56 fwd
 //    111 -> 106 us, dgrad 103 -> 99 us).
 int g_bnbwd_early = 1;  // BN-backward epilogue prefetch at kernel start for small K (A/B switch)
-// (the 64-row tile rule below depends on K too: conv_bnbwd_mtiles mirrors it)
+// (the 64-row tile rule below depends on K too; conv_bnbwd_mtiles reads it off the plan)
 
 // N-fastest tile order (N tiles folded into grid x, see conv_tap_k): 0 off, 1 by shape
 // (default), 2 every conv_tap_k launch (A/B switch).  Per call, same box
@@ -758,12 +758,40 @@ int g_bnbwd_early = 1;  // BN-backward epilogue prefetch at kernel start for sma
 // ResNet-50 (folding every 1x1 launch): 12,367 / 12,228 vs 12,174 / 12,060 img/s.
 int g_conv_nfast = 1;
 
-inline dim3 conv_grid(int mtiles, int ntiles, int nclasses, bool one_by_one) {
-  (void)one_by_one;
-  const bool fold = ntiles > 1 && (g_conv_nfast == 2 ||
-                                   (g_conv_nfast == 1 && !(ntiles == 4 && mtiles >= 1024)));
-  return fold ? dim3((unsigned)(mtiles * ntiles), 1, nclasses)
-              : dim3((unsigned)mtiles, (unsigned)ntiles, nclasses);
+// The plan of a conv_tap_k launch (ConvPlan, amd_kernels.h): the ONE place the tile, ring
+// and tile order are chosen - launch_conv_tap switches on it, conv_plan reports it.
+// epi: EPI 1 is the BN-backward epilogue; EPI 2 - 4, the stats-only and recompute forms of
+// a 1x1 forward, take EPI 0's plan (their results must be bitwise the plain launch's).
+ConvPlan tap_plan(int mode, int epi, int M, int KC, int NC) {
+  ConvPlan p{};
+  p.kernel = 0;
+  p.nclasses = mode == kDgrad3 || mode == kDgrad1 ? 4 : 1;
+  p.BM = kBM;
+  p.BN = NC % 128 == 0 ? 128 : 64;
+  bool by_grid = false;
+  if (epi == 1 && mode == kFwd1 && NC % 128 == 0 && M >= 50176 && KC < 256) {
+    // K <= 128 (two to four 32-deep K-tiles): the epilogue's loads go out at kernel start
+    // and fly under the K loop's DMA (64 -> 256 @ 56 +skip: 324 -> 307 us, 128 -> 512
+    // @ 28: 176 -> 171; at K = 256 the held registers cost a wave per SIMD: 110 -> 115)
+    p.BM = 64; p.BK = 32; p.NB = 3;
+    p.early = g_bnbwd_early && KC <= 128;
+  } else if (mode == kFwd1 && NC % 128 == 0 && KC / kBK <= 1) {
+    p.BK = kBK; p.NB = 1;
+  } else if (NC % 128 == 0) {
+    by_grid = true;
+  } else {
+    p.BK = 32; p.NB = 3;
+  }
+  p.mtiles = (M + p.BM - 1) / p.BM;
+  p.ntiles = NC / p.BN;
+  p.folded = p.ntiles > 1 && (g_conv_nfast == 2 || (g_conv_nfast == 1 &&
+                                                    !(p.ntiles == 4 && p.mtiles >= 1024)));
+  if (by_grid) {
+    const bool big = (unsigned)p.mtiles * (unsigned)p.ntiles * (unsigned)p.nclasses >= 1024;
+    p.BK = big ? 32 : kBK;
+    p.NB = big ? 3 : 2;
+  }
+  return p;
 }
 
 template <int MODE, int EPI = 0>
@@ -771,38 +799,29 @@ void launch_conv_tap(const bf16_t* a, const bf16_t* w, bf16_t* y, const ConvGeom
                      hipStream_t st, float* slab = nullptr, const float* shift = nullptr,
                      const ConvBnEpi& ep = ConvBnEpi{}) {
   if (g.M == 0) return;
-  const int nclasses = MODE == kDgrad3 || MODE == kDgrad1 ? 4 : 1;
-  constexpr bool k1 = MODE == kFwd1 || MODE == kDgrad1;
-  // (EPI 2 - 4, the stats-only and recompute forms of a 1x1 forward, take EPI 0's plan:
-  // their results must be bitwise the plain launch's)
-  if constexpr (EPI == 1 && MODE == kFwd1) {
-    if (g.NC % 128 == 0 && g.M >= 50176 && g.KC < 256) {
-      const dim3 grid = conv_grid((g.M + 63) / 64, g.NC / 128, nclasses, k1);
-      // K <= 128 (two to four 32-deep K-tiles): the epilogue's loads go out at kernel start
-      // and fly under the K loop's DMA (64 -> 256 @ 56 +skip: 324 -> 307 us, 128 -> 512
-      // @ 28: 176 -> 171; at K = 256 the held registers cost a wave per SIMD: 110 -> 115)
-      if (g_bnbwd_early && g.KC <= 128)
-        hipLaunchKernelGGL((conv_tap_k<MODE, 64, 128, 2, 2, 3, EPI, kCT, 32, true>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-      else
-        hipLaunchKernelGGL((conv_tap_k<MODE, 64, 128, 2, 2, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-      return;
+  const ConvPlan p = tap_plan(MODE, EPI, g.M, g.KC, g.NC);
+  const dim3 grid = p.folded ? dim3((unsigned)(p.mtiles * p.ntiles), 1, p.nclasses)
+                             : dim3((unsigned)p.mtiles, (unsigned)p.ntiles, p.nclasses);
+#define TAP_LAUNCH(...)                                                                        \
+  hipLaunchKernelGGL((conv_tap_k<MODE, __VA_ARGS__>), grid, dim3(kCT), 0, st, a, w, y, g, slab, \
+                     shift, ep)
+  if (p.BM == 64) {
+    if constexpr (EPI == 1 && MODE == kFwd1) {
+      if (p.early) TAP_LAUNCH(64, 128, 2, 2, 3, EPI, kCT, 32, true);
+      else TAP_LAUNCH(64, 128, 2, 2, 3, EPI, kCT, 32);
+    } else {
+      std::abort();  // tap_plan: 64-row tiles for the BN-backward 1x1 launches only
     }
-  }
-  if (MODE == kFwd1 && g.NC % 128 == 0 && g.KC / kBK <= 1) {
-    const dim3 grid = conv_grid((g.M + kBM - 1) / kBM, g.NC / 128, nclasses, k1);
-    hipLaunchKernelGGL((conv_tap_k<MODE, 128, 128, 2, 2, 1, EPI>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-  } else if (g.NC % 128 == 0) {
-    const dim3 grid = conv_grid((g.M + kBM - 1) / kBM, g.NC / 128, nclasses, k1);
-    if (grid.x * grid.y * grid.z >= 1024)
-      hipLaunchKernelGGL((conv_tap_k<MODE, 128, 128, 2, 2, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-    else
-      hipLaunchKernelGGL((conv_tap_k<MODE, 128, 128, 2, 2, 2, EPI>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
+  } else if (p.BN == 128) {
+    if (p.NB == 1) TAP_LAUNCH(128, 128, 2, 2, 1, EPI);
+    else if (p.NB == 3) TAP_LAUNCH(128, 128, 2, 2, 3, EPI, kCT, 32);
+    else TAP_LAUNCH(128, 128, 2, 2, 2, EPI);
   } else if constexpr (EPI < 2) {
-    const dim3 grid = conv_grid((g.M + kBM - 1) / kBM, g.NC / 64, nclasses, k1);
-    hipLaunchKernelGGL((conv_tap_k<MODE, 128, 64, 4, 1, 3, EPI, kCT, 32>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
+    TAP_LAUNCH(128, 64, 4, 1, 3, EPI, kCT, 32);
   } else {
     std::abort();  // conv1x1_recompute_ok: 128-wide output tiles only
   }
+#undef TAP_LAUNCH
 }
 
 // ============================================================================
@@ -1176,13 +1195,6 @@ Conv3hCfg conv3h_cfg(int N, int H, int W, int Cout, int stride) {
   }
   return best;
 }
-int conv3h_bn(int N, int H, int W, int Cout, int stride) {
-  return conv3h_cfg(N, H, W, Cout, stride).bn;
-}
-bool conv3h_ok(int N, int H, int W, int Cout, int stride) {
-  return conv3h_bn(N, H, W, Cout, stride) != 0;
-}
-int conv3h_mtile(int N, int H, int W, int Cout) { return conv3h_cfg(N, H, W, Cout, 1).bm; }
 
 // halo kernel tile order: N tiles folded into grid x, N fastest (1) or on grid y (0).
 // Neutral per call (its M tiles' windows are small next to the weights re-read per tap)
@@ -1190,16 +1202,30 @@ int conv3h_mtile(int N, int H, int W, int Cout) { return conv3h_cfg(N, H, W, Cou
 // off by default (A/B switch)
 int g_conv3h_nfast = 0;
 
+// The plan of a conv3h_k launch (kernel 1; BM = 0: the shape is not eligible): 32-channel
+// slices, the weights on a 3-deep ring.  launch_conv3h switches on it.
+ConvPlan conv3h_plan(int N, int H, int W, int Cout, int stride) {
+  const Conv3hCfg c = conv3h_cfg(N, H, W, Cout, stride);
+  ConvPlan p{};
+  p.kernel = 1;
+  p.BM = c.bm; p.BN = c.bn; p.BK = 32; p.NB = 3;
+  p.nclasses = 1;
+  if (c.bn == 0) return p;
+  p.mtiles = (int)(((int64_t)N * H * W + c.bm - 1) / c.bm);
+  p.ntiles = Cout / c.bn;
+  p.folded = g_conv3h_nfast && p.ntiles > 1;
+  return p;
+}
+
 template <int EPI>
 void launch_conv3h(const bf16_t* a, const bf16_t* w, bf16_t* y, const ConvGeom& g, int N,
                    hipStream_t st, float* slab, const float* shift, const ConvBnEpi& ep) {
-  const Conv3hCfg c = conv3h_cfg(N, g.GH, g.GW, g.NC, 1);
-  const int mtiles = (g.M + c.bm - 1) / c.bm, ntiles = g.NC / c.bn;
-  const dim3 grid = g_conv3h_nfast && ntiles > 1 ? dim3((unsigned)(mtiles * ntiles), 1, 1)
-                                                 : dim3((unsigned)mtiles, (unsigned)ntiles, 1);
-  if (c.bn == 128 && c.bm == 256)
+  const ConvPlan p = conv3h_plan(N, g.GH, g.GW, g.NC, 1);
+  const dim3 grid = p.folded ? dim3((unsigned)(p.mtiles * p.ntiles), 1, 1)
+                             : dim3((unsigned)p.mtiles, (unsigned)p.ntiles, 1);
+  if (p.BN == 128 && p.BM == 256)
     hipLaunchKernelGGL((conv3h_k<128, EPI, 256>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
-  else if (c.bn == 128)
+  else if (p.BN == 128)
     hipLaunchKernelGGL((conv3h_k<128, EPI, 224>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
   else
     hipLaunchKernelGGL((conv3h_k<64, EPI, 256>), grid, dim3(kCT), 0, st, a, w, y, g, slab, shift, ep);
@@ -1942,6 +1968,11 @@ int conv_wgrad_splits(int N, int H, int W, int Cin, int Cout, int ksize, int str
   return best;
 }
 
+void conv_wgrad_tap_tile(int Cin, int Cout, int algo, int tile[4]) {
+  const WgTapCfg c = wg_tap_cfg(Cin, Cout, algo);
+  tile[0] = c.BM; tile[1] = c.BN; tile[2] = c.BK; tile[3] = c.NB;
+}
+
 bool conv3x3_wgrad_supported(int W, int algo) { return (algo != 1 && algo != 4) || W <= kWgMaxW; }
 
 // the strip-ring kernel's shapes: 3x3 stride 1, channels % 64 (64 x 64 tiles), W <= 56
@@ -2121,15 +2152,35 @@ void conv_nfast(int mode) { g_conv_nfast = mode; }
 void conv_halo_nfast(int on) { g_conv3h_nfast = on; }
 bool conv_1x1_on_gemm4w(int64_t M, int Cin, int Cout) { return conv1x1_g4w(M, Cin, Cout, 1); }
 
-int conv_fwd_mtiles(int N, int H, int W, int Cout, int stride, int ksize, int Cin) {
+// Which kernel and plan a conv call takes (amd_kernels.h): the routing below and the slab
+// widths are read off this one function.
+ConvPlan conv_plan(int op, int N, int H, int W, int Cin, int Cout, int ksize, int stride) {
+  if (op == kConvOpDgradS2 || op == kConvOpDgradS2BnBwd) {
+    // GEMM rows = the pixels of one parity class, K = dY's channels, N = dX's channels
+    const int M = N * (H / 2) * (W / 2);
+    return tap_plan(ksize == 3 ? kDgrad3 : kDgrad1, op == kConvOpDgradS2BnBwd ? 1 : 0, M, Cout,
+                    Cin);
+  }
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const int64_t M = (int64_t)N * Ho * Wo;
-  if (ksize == 3 && conv3h_ok(N, H, W, Cout, stride)) {
-    const int bm = conv3h_mtile(N, H, W, Cout);
-    return (int)((M + bm - 1) / bm);
+  if (op == kConvOpFwd && ksize == 1 && conv1x1_g4w(M, Cin, Cout, stride)) {
+    ConvPlan p{};
+    p.kernel = 2;
+    p.BM = 256; p.BN = 256; p.BK = 64; p.NB = 2;  // gemm4w's tile: two LDS slots
+    p.mtiles = (int)((M + 255) / 256);
+    p.ntiles = Cout / 256;
+    p.nclasses = 1;
+    return p;
   }
-  if (ksize == 1 && conv1x1_g4w(M, Cin, Cout, stride)) return (int)((M + 255) / 256);
-  return (int)((M + kBM - 1) / kBM);  // launch_conv_tap's M tile (EPI 0)
+  if (ksize == 3 && stride == 1) {
+    const ConvPlan p = conv3h_plan(N, H, W, Cout, 1);
+    if (p.BM != 0) return p;
+  }
+  return tap_plan(ksize == 3 ? kFwd3 : kFwd1, op == kConvOpBnBwd ? 1 : 0, (int)M, Cin, Cout);
+}
+
+int conv_fwd_mtiles(int N, int H, int W, int Cout, int stride, int ksize, int Cin) {
+  return conv_plan(kConvOpFwd, N, H, W, Cin, Cout, ksize, stride).mtiles;
 }
 
 void conv_nhwc_fwd(const void* x, const void* w, void* y, int N, int H, int W, int Cin, int Cout,
@@ -2140,7 +2191,8 @@ void conv_nhwc_fwd(const void* x, const void* w, void* y, int N, int H, int W, i
   const auto* xp = static_cast<const bf16_t*>(x);
   const auto* wp = static_cast<const bf16_t*>(w);
   auto* yp = static_cast<bf16_t*>(y);
-  if (ksize == 1 && conv1x1_g4w((int64_t)N * Ho * Wo, Cin, Cout, stride)) {
+  const int kernel = conv_plan(kConvOpFwd, N, H, W, Cin, Cout, ksize, stride).kernel;
+  if (kernel == 2) {
     // y[M, Cout] = x[M, Cin] . W[Cout, Cin]^T (NHWC rows, KRSC weight rows)
     GemmArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -2158,7 +2210,7 @@ void conv_nhwc_fwd(const void* x, const void* w, void* y, int N, int H, int W, i
     gemm4w(a, stats_slab ? 3 : 0, st);
     return;
   }
-  if (ksize == 3 && conv3h_ok(N, H, W, Cout, stride))
+  if (kernel == 1)
     launch_conv3h<0>(xp, wp, yp, g, N, st, stats_slab, stats_shift, ConvBnEpi{});
   else if (ksize == 3) launch_conv_tap<kFwd3>(xp, wp, yp, g, st, stats_slab, stats_shift);
   else launch_conv_tap<kFwd1>(xp, wp, yp, g, st, stats_slab, stats_shift);
@@ -2190,14 +2242,7 @@ void conv1x1_bn_bwd(const void* x, const void* w, void* dx, int N, int H, int W,
 }
 
 int conv_bnbwd_mtiles(int N, int H, int W, int Cout, int ksize, int Cin) {
-  const int64_t M = (int64_t)N * H * W;
-  // launch_conv_tap's M tile with the BN-backward epilogue (64 rows for the large 1x1s)
-  if (ksize == 1 && Cout % 128 == 0 && M >= 50176 && Cin < 256) return (int)((M + 63) / 64);
-  if (ksize == 3 && conv3h_ok(N, H, W, Cout, 1)) {
-    const int bm = conv3h_mtile(N, H, W, Cout);
-    return (int)((M + bm - 1) / bm);
-  }
-  return (int)((M + kBM - 1) / kBM);
+  return conv_plan(kConvOpBnBwd, N, H, W, Cin, Cout, ksize, 1).mtiles;
 }
 void conv_nhwc_fwd_bnbwd(const void* dy, const void* w, void* gout, int N, int H, int W, int Cin,
                          int Cout, int ksize, int stride, const ConvBnEpi& ep, float* slab,
@@ -2207,7 +2252,7 @@ void conv_nhwc_fwd_bnbwd(const void* dy, const void* w, void* gout, int N, int H
   const auto* xp = static_cast<const bf16_t*>(dy);
   const auto* wp = static_cast<const bf16_t*>(w);
   auto* yp = static_cast<bf16_t*>(gout);
-  if (ksize == 3 && stride == 1 && conv3h_ok(N, H, W, Cout, 1))
+  if (conv_plan(kConvOpBnBwd, N, H, W, Cin, Cout, ksize, stride).kernel == 1)
     launch_conv3h<1>(xp, wp, yp, g, N, st, slab, nullptr, ep);
   else if (ksize == 3) launch_conv_tap<kFwd3, 1>(xp, wp, yp, g, st, slab, nullptr, ep);
   else launch_conv_tap<kFwd1, 1>(xp, wp, yp, g, st, slab, nullptr, ep);
@@ -2233,8 +2278,8 @@ void conv_nhwc_dgrad_s2(const void* dy, const void* wt, void* dx, int N, int H, 
 // that BN's backward sums, slab [2][Cin][4 * ceil(N*Ho*Wo / 128)] (every input pixel belongs
 // to exactly one parity class, so each g is final in its epilogue)
 int conv_dgrad_s2_bnbwd_mtiles(int N, int H, int W) {
-  const int64_t M = (int64_t)N * (H / 2) * (W / 2);
-  return 4 * (int)((M + kBM - 1) / kBM);
+  // (the tile height does not depend on the channel counts in this mode)
+  return 4 * conv_plan(kConvOpDgradS2BnBwd, N, H, W, 64, 64, 3, 2).mtiles;
 }
 void conv_nhwc_dgrad_s2_bnbwd(const void* dy, const void* wt, void* gout, int N, int H, int W,
                               int Cin, int Cout, const ConvBnEpi& ep, float* slab,

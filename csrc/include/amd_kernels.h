@@ -350,6 +350,21 @@ void conv_nhwc_fwd(const void* x, const void* w, void* y, int N, int H, int W, i
                    int ksize, int stride, hipStream_t st, float* stats_slab = nullptr,
                    const float* stats_shift = nullptr);
 int conv_fwd_mtiles(int N, int H, int W, int Cout, int stride, int ksize, int Cin);
+// The launch plan of a conv call on the own kernels.  conv_plan is the one place it is
+// chosen: the launchers switch on its result, the slab widths are its mtiles, and Python
+// reads it (conv.tap_plan) so a test can assert which plan its shape ran.
+struct ConvPlan {
+  int kernel;          // 0 conv_tap_k, 1 conv3h_k (LDS-resident halo), 2 gemm4w
+  int BM, BN, BK, NB;  // output tile, K-tile depth, DMA ring depth
+  int early;           // BN-backward epilogue: operands prefetched at kernel start
+  int folded;          // N tiles folded into grid x (N fastest)
+  int mtiles, ntiles, nclasses;
+};
+// op: forward (with or without statistics), stride-1 data gradient with the BN-backward
+// epilogue (Cin = dY's channels, Cout = the gradient's), stride-2 data gradient without /
+// with that epilogue (N, H, W, Cin of dX, Cout of dY as conv_nhwc_dgrad_s2)
+enum ConvOp { kConvOpFwd = 0, kConvOpBnBwd = 1, kConvOpDgradS2 = 2, kConvOpDgradS2BnBwd = 3 };
+ConvPlan conv_plan(int op, int N, int H, int W, int Cin, int Cout, int ksize, int stride);
 // M tiles (slab rows) of conv_nhwc_fwd_bnbwd's stride-1 launch
 int conv_bnbwd_mtiles(int N, int H, int W, int Cout, int ksize, int Cin);
 // BatchNorm-backward epilogue of a data-gradient conv (conv_nhwc_fwd on dY with the
@@ -433,6 +448,8 @@ void conv_nhwc_dgrad_s2_bnbwd(const void* dy, const void* wt, void* gout, int N,
 // 1 = all-9-taps strip kernel (3x3 stride 1, W <= 56), 4 = 64-channel strip-ring kernel
 // (3x3 stride 1, Cin = Cout = 64, W <= 56: conv3x3_wgrad_c64_ok)
 int conv_wgrad_splits(int N, int H, int W, int Cin, int Cout, int ksize, int stride, int algo);
+// tile {BM, BN, BK, NB} of the per-tap kernel (algo 0, 2, 3, 5) for these channel counts
+void conv_wgrad_tap_tile(int Cin, int Cout, int algo, int tile[4]);
 bool conv3x3_wgrad_supported(int W, int algo);
 bool conv3x3_wgrad_c64_ok(int W, int Cin, int Cout, int ksize, int stride);
 int64_t conv_wgrad_workspace(int S, int Cin, int Cout, int ksize);  // floats

@@ -181,6 +181,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   conv.def("rot_weight", &conv3x3_rot_weight_op);
   conv.def("transpose_weight", &conv1x1_transpose_weight_op);
   conv.def("prep_weights", &conv_prep_weights_op);
+  // read-only plan queries (what the launchers themselves switch on): tests assert through
+  // them that a shape ran the plan it was chosen for
+  conv.def(
+      "tap_plan",
+      [](const std::string& op, int N, int H, int W, int Cin, int Cout, int ksize, int stride) {
+        const int o = op == "fwd" ? kConvOpFwd : op == "bnbwd" ? kConvOpBnBwd
+                      : op == "dgrad_s2" ? kConvOpDgradS2
+                      : op == "dgrad_s2_bnbwd" ? kConvOpDgradS2BnBwd : -1;
+        TORCH_CHECK(o >= 0, "tap_plan: op is 'fwd', 'bnbwd', 'dgrad_s2' or 'dgrad_s2_bnbwd'");
+        TORCH_CHECK((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && N > 0 &&
+                        H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 64 == 0,
+                    "tap_plan: 1x1 / 3x3, stride 1 / 2, channels x64");
+        const ConvPlan p = conv_plan(o, N, H, W, Cin, Cout, ksize, stride);
+        static const char* const names[] = {"conv_tap_k", "conv3h_k", "gemm4w"};
+        return py::make_tuple(names[p.kernel], p.BM, p.BN, p.BK, p.NB, p.early != 0,
+                              p.folded != 0);
+      },
+      py::arg("op"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"), py::arg("Cout"),
+      py::arg("ksize"), py::arg("stride") = 1,
+      "(kernel, BM, BN, BK, NB, early, folded) of the conv call's launch");
+  conv.def("wgrad_splits", &conv_wgrad_splits, py::arg("N"), py::arg("H"), py::arg("W"),
+           py::arg("Cin"), py::arg("Cout"), py::arg("ksize"), py::arg("stride"), py::arg("algo"));
+  conv.def(
+      "wgrad_tap_tile",
+      [](int Cin, int Cout, int algo) {
+        int t[4];
+        conv_wgrad_tap_tile(Cin, Cout, algo, t);
+        return py::make_tuple(t[0], t[1], t[2], t[3]);
+      },
+      py::arg("Cin"), py::arg("Cout"), py::arg("algo"), "(BM, BN, BK, NB) of the per-tap kernel");
+  conv.def("stem_wgrad_splits", &stem_wgrad_splits, py::arg("N"), py::arg("H"));
   conv.def("set_nfast", &conv_nfast, py::arg("mode"));
   conv.def("set_halo_nfast", &conv_halo_nfast, py::arg("on"));
   conv.def("set_halo", &conv_halo_enable, py::arg("mode"),
