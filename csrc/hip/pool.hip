@@ -2,7 +2,8 @@
 //
 // Forward: a thread owns 8 consecutive channels (one 16-byte load per window
 // tap, VEC path; scalar path for C % 8 != 0) of one output pixel, scans the
-// window in (kh, kw) order keeping the FIRST maximum (NaN propagates, as torch),
+// window in (kh, kw) order keeping the FIRST maximum (NaN propagates, as torch; a
+// window whose values are all -inf keeps its first in-bounds tap, as torch),
 // writes y and the winning tap index as one byte per element (kh*k + kw).
 // BN variant (ResNet stem): the window values are relu(x * scale + shift) with the
 // BatchNorm's per-channel affine applied on load - the BN + ReLU output is never
@@ -44,12 +45,16 @@ __global__ void __launch_bounds__(kPoolThreads)
     pix /= OW;
     const int oh = (int)(pix % OH);
     const int n = (int)(pix / OH);
+    const int h0 = oh * s - p, w0 = ow * s - p;
+    // a window with no value above -inf keeps its first IN-BOUNDS tap (tap 0 may be
+    // padding, which no input matches in the backward: the gradient would be dropped)
+    const int first = (h0 < 0 ? -h0 : 0) * k + (w0 < 0 ? -w0 : 0);
     float best[V];
     int arg[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       best[i] = -INFINITY;
-      arg[i] = 0;
+      arg[i] = first;
     }
     float sc[V], sh[V];
     if constexpr (BN) {
@@ -60,7 +65,6 @@ __global__ void __launch_bounds__(kPoolThreads)
         sh[i] = (bn.b ? bn.b[c] : 0.f) - bn.mean[c] * sc[i];
       }
     }
-    const int h0 = oh * s - p, w0 = ow * s - p;
     for (int kh = 0; kh < k; ++kh) {
       const int h = h0 + kh;
       if (h < 0 || h >= H) continue;
@@ -223,12 +227,14 @@ __global__ void __launch_bounds__(kPoolThreads)
         sh[i] = s_sh[cv * 8 + i];
       }
     }
+    // first in-bounds tap, kept by a window with no value above -inf (see maxpool_fwd_k)
+    const int first = (oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0);
     float best[8];
     int arg[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       best[i] = -INFINITY;
-      arg[i] = 0;
+      arg[i] = first;
     }
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {

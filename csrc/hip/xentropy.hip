@@ -122,7 +122,9 @@ __global__ void __launch_bounds__(kXT)
     float l = 0.f;
     if (!ignored(lab, padding_idx, V)) {
       const float xl = to_f32(xr[lab]);
-      l = lse - (1.f - smoothing) * xl - smoothing * TT / (float)V;
+      // without smoothing the mean does not enter: 0 * TT is NaN for a row with -inf logits
+      const float sm = smoothing != 0.f ? smoothing * TT / (float)V : 0.f;
+      l = lse - (1.f - smoothing) * xl - sm;
     }
     loss[row] = from_f32<TO>(l);
     lse_out[row] = lse;

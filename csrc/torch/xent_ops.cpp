@@ -27,7 +27,9 @@ std::tuple<at::Tensor, at::Tensor> xentropy_fwd_op(at::Tensor logits, at::Tensor
     at::Tensor ign = ignored_rows(labels, padding_idx, V);
     at::Tensor safe = at::where(ign, at::zeros_like(labels), labels);
     at::Tensor xl = xf.gather(1, safe.unsqueeze(1)).squeeze(1);
-    at::Tensor loss = lse - (1.0 - smoothing) * xl - smoothing * xf.mean(1);
+    at::Tensor loss = lse - (1.0 - smoothing) * xl;
+    // without smoothing the mean does not enter: 0 * mean is NaN for a row with -inf logits
+    if (smoothing != 0.0) loss = loss - smoothing * xf.mean(1);
     loss = at::where(ign, at::zeros_like(loss), loss);
     return {loss.to(lossT), lse};
   }
