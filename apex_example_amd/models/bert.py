@@ -4,6 +4,8 @@ attention kernels (ops/attention.py, with the padding mask applied inside them;
 PyTorch SDPA off-GPU, in fp32 or with fused_attention=False), masked-LM head on the
 gathered masked positions only (NVIDIA's pretraining recipe, max_predictions
 per sequence) with the decoder tied to the word embeddings, and the NSP head.
+``BertConfig(unpad=True)`` runs the encoder layers on the non-padding tokens only (packed
+sequences, attention per sequence through ``cu_seqlens``; contrib/fmha).
 
 bert_large(): 24 layers, hidden 1024, 16 heads, FFN 4096, vocab 30522 (padded to
 a multiple of 8 optionally), 512 positions.
@@ -46,6 +48,10 @@ class BertConfig:
     # < 1e-3, below bf16 resolution at FFN magnitudes) or "gelu" (erf).  The stock
     # path (fused_dense=False) uses the same function, so comparisons stay like for like.
     hidden_act: str = "gelu_tanh"
+    # Unpadded encoder: with an attention_mask, run the layers on the kept tokens only,
+    # packed into one [1, T, hidden] buffer, attention per sequence through cu_seqlens
+    # (contrib.fmha); the padded positions of the output are zero.  See BertModel.forward.
+    unpad: bool = False
 
 
 def _ln(cfg, n):
@@ -85,19 +91,27 @@ class BertSelfAttention(nn.Module):
     def _lin(self, m, x):
         return fused_dense_function(x, m.weight, m.bias) if self.fused_dense else m(x)
 
-    def forward(self, x, attn_mask=None, key_mask=None):
+    def forward(self, x, attn_mask=None, key_mask=None, cu_seqlens=None, max_s=None):
         """Returns (attention output, x as the residual branch).  With fused_dense the
         residual is the QKV layer's skip output, so the input gradient of the block
         is one accumulating GEMM (no separate residual-gradient add).  attn_mask: additive
         [b, 1, 1, s] for the SDPA path; key_mask: the same padding mask prepared for the
-        fused kernels (ops.attention.PreparedKeyMask), which then take it instead."""
+        fused kernels (ops.attention.PreparedKeyMask), which then take it instead.
+        cu_seqlens / max_s: x is [1, T, hidden], the packed tokens of the sequences that
+        cu_seqlens (int32 [B + 1]) delimits, each attending within itself (no mask)."""
         b, s, hd = x.shape
         if self.fused_dense:
             qkv, skip = fused_dense_skip_function(x, self.qkv.weight, self.qkv.bias)
         else:
             qkv, skip = self.qkv(x), x
-        qkv = qkv.view(b, s, 3, self.h, self.d)
         p = self.p if self.training else 0.0
+        if cu_seqlens is not None:
+            from ..contrib.fmha import packed_self_attention
+
+            o = packed_self_attention(qkv.view(b * s, 3, self.h, self.d), cu_seqlens, max_s, p,
+                                      fused=self.fused)
+            return self._lin(self.dense, o.reshape(b, s, hd)), skip
+        qkv = qkv.view(b, s, 3, self.h, self.d)
         if (self.fused and (attn_mask is None or key_mask is not None)
                 and fused_attn.supported(qkv, self.d)):
             o = fused_attn.fused_attention_qkv(qkv, causal=False, dropout_p=p, key_bias=key_mask)
@@ -124,8 +138,8 @@ class BertLayer(nn.Module):
         self.fused_dense = cfg.fused_dense
         self.approximate = {"gelu_tanh": "tanh", "gelu": "none"}[cfg.hidden_act]
 
-    def forward(self, x, attn_mask=None, key_mask=None):
-        a, x = self.attention(x, attn_mask, key_mask)
+    def forward(self, x, attn_mask=None, key_mask=None, cu_seqlens=None, max_s=None):
+        a, x = self.attention(x, attn_mask, key_mask, cu_seqlens, max_s)
         x, _ = fused_add_dropout_layer_norm(x, a, self.attn_ln, self.attn_dropout.p,
                                             self.training)
         if self.fused_dense:
@@ -154,7 +168,18 @@ class BertModel(nn.Module):
         self.pooler = nn.Linear(cfg.hidden_size, cfg.hidden_size)
 
     def forward(self, input_ids, token_type_ids, attention_mask=None):
+        """Returns (sequence output [b, s, hidden], pooled output [b, hidden]).
+
+        config.unpad with an attention_mask ([b, s], non-zero = keep, any pattern): the kept
+        tokens, in order and with their own position embeddings, are gathered after the
+        embeddings into one [1, T, hidden] buffer, every layer (GEMMs, LayerNorms, attention
+        per sequence) runs on those T rows alone, and the result is scattered back into a
+        zero [b, s, hidden] before the pooler - padded positions of the sequence output
+        are exactly zero.  Costs ONE host sync per forward (the per-sequence token counts:
+        T and the longest sequence size the buffers and the attention grid)."""
         x = self.embeddings(input_ids, token_type_ids)
+        if self.config.unpad and attention_mask is not None:
+            return self._forward_unpadded(x, attention_mask)
         mask = key_mask = None
         if attention_mask is not None:
             # [b, s] 1 = keep -> additive [b, 1, 1, s]
@@ -169,6 +194,22 @@ class BertModel(nn.Module):
                     additive_attention_mask(attention_mask, torch.float32))
         for layer in self.layers:
             x = layer(x, mask, key_mask)
+        pooled = torch.tanh(self.pooler(x[:, 0]))
+        return x, pooled
+
+    def _forward_unpadded(self, x, attention_mask):
+        b, s, hd = x.shape
+        keep = attention_mask.reshape(-1) != 0
+        counts = keep.view(b, s).sum(1)
+        lens = counts.tolist()  # the host sync
+        T, max_s = sum(lens), max(lens + [1])
+        cu_seqlens = F.pad(counts.cumsum(0), (1, 0)).to(torch.int32)
+        # attention_mask.flatten().nonzero(), its size known from the counts (no second sync)
+        idx = torch.nonzero_static(keep, size=T).squeeze(1)
+        t = x.reshape(b * s, hd).index_select(0, idx).unsqueeze(0)
+        for layer in self.layers:
+            t = layer(t, cu_seqlens=cu_seqlens, max_s=max_s)
+        x = x.new_zeros(b * s, hd).index_copy(0, idx, t.squeeze(0)).view(b, s, hd)
         pooled = torch.tanh(self.pooler(x[:, 0]))
         return x, pooled
 

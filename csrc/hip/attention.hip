@@ -45,6 +45,16 @@
 // ride the K/V DMA ring; a dK/dV workgroup loads its lanes' biases once and writes
 // zeros when its 128 keys are all dead.  The KMASK=false instantiations are the
 // mask-free kernels unchanged.
+//
+// Packed sequences (VARLEN kernels, KMASK = false only): q, k, v, o and the gradients are
+// [T, H, 64] views of the real tokens of B sequences, sequence b owning rows cu[b] ..
+// cu[b+1]-1 of an int32 offsets vector read on the device.  A workgroup reads its
+// sequence's first row and length (two scalar loads), uses the length as Sq = Sk, rebases
+// every per-batch pointer by first row * token stride in place of b * batch stride, and
+// returns at once when its tile lies past the length; queries, keys and the dropout hash
+// keep their sequence-local indices, lse / D their [B, H, Sp] rows with Sp from the
+// launch's max_seqlen, which also sizes the grid.  The VARLEN = false instantiations are
+// the kernels unchanged.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -249,6 +259,8 @@ struct AttnArgs {
   uint32_t seed;
   const float* kbias;          // KMASK: [B][key_stride] log2-unit key bias
   const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
+  const int* cu;               // VARLEN: [B + 1] first token row of each sequence
+  int T;                       // VARLEN: rows of the packed views
 };
 
 // ------------------------------------------------------------------- key-mask prepare
@@ -299,6 +311,29 @@ struct LiveTiles {
 };
 
 // ---------------------------------------------------------------------------- forward
+// VARLEN: sequence b of a packed batch, rows cu[b] .. cu[b + 1] - 1 of [T, H, 64] views -
+// two scalar loads, wave-uniform.  The length is clipped to the launch's max_seqlen (the
+// rows lse / D have) and to the T rows the views hold, so whatever cu contains no row
+// outside the views or the lse rows is touched; a workgroup whose tile starts at or past
+// the length has nothing to do (false: the caller returns before any clamp, DMA or
+// barrier - the row clamps index row -1 at length 0).
+__device__ __forceinline__ bool varlen_seq(const int* cu, int b, int T, int max_len, int tile0,
+                                           int& s0, int& len) {
+  s0 = cu[b];
+  int l = cu[b + 1] - s0;
+  l = l < max_len ? l : max_len;
+  l = l < T - s0 ? l : T - s0;
+  len = l;
+  return s0 >= 0 && tile0 < l;
+}
+// element offset of batch element b (stride sb) or, VARLEN, of the sequence whose first
+// row is s0 (row stride ss)
+template <bool VARLEN>
+__device__ __forceinline__ int64_t seq_off(int b, int s0, int64_t sb, int64_t ss) {
+  if constexpr (VARLEN) return (int64_t)s0 * ss;
+  else return b * sb;
+}
+
 // Block -> (tile, b*H+h).  Dispatch order is the flattened block id (x fastest) and
 // consecutive ids go to consecutive XCDs, so: (1) the tiles of one head are gridDim.y
 // ids apart - the same XCD whenever B*H % 8 == 0, so that head's K/V (fwd, dQ) or
@@ -322,11 +357,11 @@ __device__ __forceinline__ float max_halves(float x) {
   return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
 }
 
-template <typename T, bool CAUSAL, bool DROP, bool KMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
 __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
-  const int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
+  int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int KV = 2 * kAKT * kARow;          // K and V images of one tile
@@ -339,14 +374,19 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   tile_of_block(CAUSAL, true, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
   const int qb0 = tile * 128;
+  [[maybe_unused]] int s0 = 0;
+  if constexpr (VARLEN) {
+    if (!varlen_seq(a.cu, b, a.T, a.Sq, qb0, s0, Sq)) return;
+    Sk = Sq;
+  }
   const int q = qb0 + wid * 32 + c32;  // this lane's query
   // dropout lattice point of (q, key quad hl) at key tile 0
   const uint32_t dbase = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)q * kDropQ +
                                     (uint32_t)hl * kDropK
                               : 0u;
-  const T* Q = static_cast<const T*>(a.q) + b * a.qsb + hh * a.qsh;
-  const T* K = static_cast<const T*>(a.k) + b * a.ksb + hh * a.ksh;
-  const T* V = static_cast<const T*>(a.v) + b * a.vsb + hh * a.vsh;
+  const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
+  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh;
+  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh;
 
   // Q^T fragments (B operand of S^T = K . Q^T): d = 16s + 8hl + j
   v8 qf[4];
@@ -576,7 +616,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   const float lt = l + __shfl_xor(l, 32);
   const float inv = lt > 0.f ? (DROP ? a.inv_keep : 1.f) / lt : 0.f;
   if (q < Sq) {
-    store_dT<T>(static_cast<T*>(a.o) + (((int64_t)b * Sq + q) * a.H + hh) * kAD, o, hl, inv);
+    const int64_t orow = VARLEN ? (int64_t)s0 + q : (int64_t)b * Sq + q;
+    store_dT<T>(static_cast<T*>(a.o) + (orow * a.H + hh) * kAD, o, hl, inv);
     if (hl == 0) a.lse[(int64_t)bh * a.lse_stride + q] = m + log2f(lt);
   }
 }
@@ -604,6 +645,8 @@ struct AttnBwdArgs {
   uint32_t seed;
   const float* kbias;          // KMASK: [B][key_stride] log2-unit key bias
   const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
+  const int* cu;               // VARLEN: [B + 1] first token row of each sequence
+  int T;                       // VARLEN: rows of the packed views
 };
 
 // A query none of whose keys is live has lse = -inf (or whatever the caller stored);
@@ -622,11 +665,11 @@ __device__ __forceinline__ float lse_guard(float lse) { return lse == -INFINITY 
 // make the compiler's vmcnt waits drain the prefetch).  KMASK: a lane's key bias is
 // loop-invariant (one load); a workgroup whose 128 keys are all dead writes zeros and
 // leaves, a wave whose 32 keys are all dead keeps the ring's barriers and skips the math.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
-  const int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
+  int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;     // 8 KiB
@@ -639,6 +682,11 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   tile_of_block(CAUSAL, false, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
   const int kb0 = tile * 128;
+  [[maybe_unused]] int s0 = 0;
+  if constexpr (VARLEN) {
+    if (!varlen_seq(a.cu, b, a.T, a.Sq, kb0, s0, Sq)) return;
+    Sk = Sq;
+  }
   const int kw0 = kb0 + wid * 32;
   const int key = kw0 + c32;
   const int kk = key < Sk ? key : Sk - 1;
@@ -667,8 +715,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   const uint32_t kdrop = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)(key >> 2) * kDropK +
                                     (uint32_t)(key & 3) * kDropQ
                               : 0u;
-  const T* Q = static_cast<const T*>(a.q) + b * a.qsb + hh * a.qsh;
-  const T* dO = static_cast<const T*>(a.dout) + b * a.dsb + hh * a.dsh;
+  const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
+  const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + hh * a.dsh;
   // KMASK: the guarded copy of lse that the dQ kernel left behind D
   const float* lse = (KMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
                      (int64_t)bh * a.lse_stride;
@@ -677,8 +725,10 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   // K^T / V^T fragments (B operands): key = this lane's column, d = 16s + 8hl + j
   v8 kf[4], vf[4];
   {
-    const T* K = static_cast<const T*>(a.k) + b * a.ksb + hh * a.ksh + (int64_t)kk * a.kss;
-    const T* V = static_cast<const T*>(a.v) + b * a.vsb + hh * a.vsh + (int64_t)kk * a.vss;
+    const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh +
+                 (int64_t)kk * a.kss;
+    const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh +
+                 (int64_t)kk * a.vss;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       kf[s] = *reinterpret_cast<const v8*>(K + 16 * s + 8 * hl);
@@ -850,10 +900,12 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   }
 
   if (key < Sk) {
-    store_dT<T>(static_cast<T*>(a.dv) + b * a.dvsb + (int64_t)key * a.dvss + hh * a.dvsh, dv, hl,
-                DROP ? a.inv_keep : 1.f);
-    store_dT<T>(static_cast<T*>(a.dk) + b * a.dksb + (int64_t)key * a.dkss + hh * a.dksh, dk, hl,
-                a.scale);
+    store_dT<T>(static_cast<T*>(a.dv) + seq_off<VARLEN>(b, s0, a.dvsb, a.dvss) +
+                    (int64_t)key * a.dvss + hh * a.dvsh,
+                dv, hl, DROP ? a.inv_keep : 1.f);
+    store_dT<T>(static_cast<T*>(a.dk) + seq_off<VARLEN>(b, s0, a.dksb, a.dkss) +
+                    (int64_t)key * a.dkss + hh * a.dksh,
+                dk, hl, a.scale);
   }
 }
 
@@ -863,11 +915,11 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
 // K sits in LDS as a row image (A of S^T) and a transposed image (A of dQ^T);
 // V as a row image (A of dP^T = V . dO^T).  KMASK: the tile's bias rides the ring and
 // dead tiles are skipped as in the forward.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
-  const int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
+  int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;
@@ -880,18 +932,25 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   tile_of_block(CAUSAL, true, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
   const int qb0 = tile * 128;
+  [[maybe_unused]] int s0 = 0;
+  if constexpr (VARLEN) {
+    if (!varlen_seq(a.cu, b, a.T, a.Sq, qb0, s0, Sq)) return;
+    Sk = Sq;
+  }
   const int q = qb0 + wid * 32 + c32;
   const int qq = q < Sq ? q : Sq - 1;
   const uint32_t dbase = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)q * kDropQ +
                                     (uint32_t)hl * kDropK
                               : 0u;
-  const T* K = static_cast<const T*>(a.k) + b * a.ksb + hh * a.ksh;
-  const T* V = static_cast<const T*>(a.v) + b * a.vsb + hh * a.vsh;
+  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh;
+  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh;
 
   v8 qf[4], of[4];
   {
-    const T* Qp = static_cast<const T*>(a.q) + b * a.qsb + hh * a.qsh + (int64_t)qq * a.qss;
-    const T* Op = static_cast<const T*>(a.dout) + b * a.dsb + hh * a.dsh + (int64_t)qq * a.dss;
+    const T* Qp = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh +
+                  (int64_t)qq * a.qss;
+    const T* Op = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) +
+                  hh * a.dsh + (int64_t)qq * a.dss;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       qf[s] = *reinterpret_cast<const v8*>(Qp + 16 * s + 8 * hl);
@@ -905,7 +964,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   // dK / dV kernel, which runs after this one (no separate preprocess launch)
   float D_q;
   {
-    const T* Opr = static_cast<const T*>(a.o) + b * a.osb + hh * a.osh + (int64_t)qq * a.oss;
+    const T* Opr = static_cast<const T*>(a.o) + seq_off<VARLEN>(b, s0, a.osb, a.oss) + hh * a.osh +
+                   (int64_t)qq * a.oss;
     float part = 0.f;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -1102,8 +1162,9 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     if (hl == 0 && q < Sq) a.D[(int64_t)bh * a.lse_stride + q] = D_q + dD;
   }
   if (q < Sq)
-    store_dT<T>(static_cast<T*>(a.dq) + b * a.dqsb + (int64_t)q * a.dqss + hh * a.dqsh, dq, hl,
-                a.scale);
+    store_dT<T>(static_cast<T*>(a.dq) + seq_off<VARLEN>(b, s0, a.dqsb, a.dqss) +
+                    (int64_t)q * a.dqss + hh * a.dqsh,
+                dq, hl, a.scale);
 }
 
 // host: the byte threshold of a dropout rate (round(256 p); p >= 255.5 / 256 drops all)
@@ -1139,6 +1200,13 @@ void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, fl
 
 // the causal mask is defined for one shared length only (no alignment convention for
 // unequal ones); the torch binding refuses the call before it gets here
+static void require_no_mask_when_packed(const char* who, const AttnProblem& p) {
+  if (p.cu_seqlens != nullptr && (p.kbias != nullptr || p.Sq != p.Sk || p.T < 0)) {
+    fprintf(stderr, "%s: a packed problem (cu_seqlens) takes no key mask and one max_seqlen\n",
+            who);
+    abort();
+  }
+}
 static void require_causal_square(const char* who, bool causal, int Sq, int Sk) {
   if (causal && Sq != Sk) {
     fprintf(stderr, "%s: causal needs equal query and key lengths, got Sq = %d, Sk = %d\n", who,
@@ -1155,6 +1223,7 @@ namespace {
 template <typename A>
 A kernel_args(const char* who, const AttnProblem& p) {
   require_causal_square(who, p.causal, p.Sq, p.Sk);
+  require_no_mask_when_packed(who, p);
   A a{};
   a.q = p.q.p; a.qsb = p.q.sb; a.qss = p.q.ss; a.qsh = p.q.sh;
   a.k = p.k.p; a.ksb = p.k.sb; a.kss = p.k.ss; a.ksh = p.k.sh;
@@ -1167,28 +1236,34 @@ A kernel_args(const char* who, const AttnProblem& p) {
   a.inv_keep = a.thr8 >= 256u ? 0.f : 256.f / (256.f - (float)a.thr8);
   a.seed = p.seed;
   a.kbias = p.kbias; a.klive = p.klive;
+  a.cu = p.cu_seqlens; a.T = p.T;
   return a;
 }
 
 template <typename T> struct Elem { using type = T; };
 
-// f(Elem<T>, causal, drop, kmask), the three switches as std::bool_constants: the
-// 2 x 2 x 2 x 2 kernel instantiations over a problem's dtype and options
+// f(Elem<T>, causal, drop, kmask, varlen), the switches as std::bool_constants: the
+// 2 x 2 x 2 x 3 kernel instantiations over a problem's dtype and options ({plain, key
+// mask, packed}: a packed problem has no key mask)
 template <typename F>
 void dispatch(const AttnProblem& p, bool drop, F f) {
   auto flag = [](bool on, auto g) { on ? g(std::true_type{}) : g(std::false_type{}); };
   auto flags = [&](auto t) {
     flag(p.causal, [&](auto c) {
-      flag(drop, [&](auto d) { flag(p.kbias != nullptr, [&](auto m) { f(t, c, d, m); }); });
+      flag(drop, [&](auto d) {
+        if (p.cu_seqlens != nullptr) f(t, c, d, std::false_type{}, std::true_type{});
+        else flag(p.kbias != nullptr, [&](auto m) { f(t, c, d, m, std::false_type{}); });
+      });
     });
   };
   if (p.dtype == DType::BF16) flags(Elem<bf16_t>{});
   else flags(Elem<half_t>{});
 }
 
-// the kernel `name` instantiated for dispatch's (t, c, d, m)
-#define ATTN_KERNEL(name) \
-  name<typename decltype(t)::type, decltype(c)::value, decltype(d)::value, decltype(m)::value>
+// the kernel `name` instantiated for dispatch's (t, c, d, m, vl)
+#define ATTN_KERNEL(name)                                                                    \
+  name<typename decltype(t)::type, decltype(c)::value, decltype(d)::value, decltype(m)::value, \
+       decltype(vl)::value>
 
 }  // namespace
 
@@ -1196,7 +1271,7 @@ void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
   AttnArgs a = kernel_args<AttnArgs>("attn_fwd", p);
   a.o = o; a.lse = lse;
   dim3 grid((p.Sq + 127) / 128, p.B * p.H), block(kAT);
-  dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m) {
+  dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m, auto vl) {
     hipLaunchKernelGGL((ATTN_KERNEL(attn_fwd_k)), grid, block, 0, st, a);
   });
 }
@@ -1212,7 +1287,7 @@ void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
   a.scale = p.scale;
   // dQ owns 128-query tiles, dK/dV 128-key tiles; dQ first (it writes D), then dK/dV
   dim3 qgrid((p.Sq + 127) / 128, p.B * p.H), kgrid((p.Sk + 127) / 128, p.B * p.H), block(kAT);
-  dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m) {
+  dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m, auto vl) {
     hipLaunchKernelGGL((ATTN_KERNEL(attn_bwd_dq_k)), qgrid, block, 0, st, a);
     hipLaunchKernelGGL((ATTN_KERNEL(attn_bwd_dkdv_k)), kgrid, block, 0, st, a);
   });

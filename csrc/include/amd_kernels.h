@@ -516,6 +516,14 @@ struct AttnProblem {
   // prepared key mask (attn_prepare_key_mask) of the Sk keys, both null = none
   const float* kbias = nullptr;          // [B][attn_lse_stride(Sk)]
   const unsigned char* klive = nullptr;  // [B][attn_lse_stride(Sk) / 64]
+  // Packed variable-length sequences: when set, q / k / v (and the backward's o, dout, dq,
+  // dk, dv) are [T, H, 64] views (sb unused, ss = the token stride), sequence b owns rows
+  // cu_seqlens[b] .. cu_seqlens[b + 1] - 1 and attends within itself, B is the number of
+  // sequences and Sq = Sk = max_seqlen >= every length (it sizes the grid and the lse
+  // rows; results do not depend on it).  int32 [B + 1] on the device, read by the kernels
+  // (no host copy).  No key mask.  Lengths are clipped to max_seqlen and to T on the device.
+  const int32_t* cu_seqlens = nullptr;
+  int T = 0;  // rows of the packed views
 };
 // Row stride of lse / D (S = Sq) and of the prepared key mask (S = Sk): S rounded up to
 // a multiple of 64.

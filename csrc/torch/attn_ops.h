@@ -36,4 +36,25 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
                  c10::optional<at::Tensor> key_bias = c10::nullopt,
                  c10::optional<at::Tensor> key_live = c10::nullopt);
 
+// Packed variable-length sequences.  q, k, v: [T, H, 64] bf16/fp16 views of the real
+// tokens of B sequences (head dim contiguous, 16-B aligned rows, any token / head strides,
+// one T, H and dtype); cu_seqlens: contiguous int32 [B + 1] on q's device, read by the
+// kernels (no host copy): sequence b owns rows cu[b] .. cu[b+1]-1 and attends within
+// itself (causal per sequence).  max_seqlen >= every length sizes the grid and lse; the
+// results do not depend on it.  Returns (o [T, H, 64] contiguous, lse [B, H, max_seqlen]
+// fp32 log2 units, rows past a sequence's length unspecified; a view of a row-padded
+// [B, H, round_up(max_seqlen, 64)] buffer).  T == 0 launches nothing; B == 0 gives o = 0.
+std::tuple<at::Tensor, at::Tensor> attn_fwd_varlen_op(at::Tensor q, at::Tensor k, at::Tensor v,
+                                                      at::Tensor cu_seqlens, int64_t max_seqlen,
+                                                      bool causal, double dropout, int64_t seed,
+                                                      double scale);
+
+// Writes rows cu[b] .. cu[b+1]-1 of dq, dk, dv (caller-allocated strided [T, H, 64] views,
+// e.g. slices of one packed dqkv buffer) for every sequence b and nothing else.  B == 0
+// writes zeros without a launch.
+void attn_bwd_varlen_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                        at::Tensor lse, at::Tensor cu_seqlens, int64_t max_seqlen, bool causal,
+                        double dropout, int64_t seed, double scale, at::Tensor dq, at::Tensor dk,
+                        at::Tensor dv);
+
 }  // namespace amd

@@ -109,6 +109,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
            py::arg("key_bias") = py::none(), py::arg("key_live") = py::none());
   attn.def("prepare_key_mask", &attn_prepare_key_mask_op, py::arg("mask"), py::arg("S"));
+  attn.def("fwd_varlen", &attn_fwd_varlen_op, py::arg("q"), py::arg("k"), py::arg("v"),
+           py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("dropout"),
+           py::arg("seed"), py::arg("scale"));
+  attn.def("bwd_varlen", &attn_bwd_varlen_op, py::arg("dout"), py::arg("q"), py::arg("k"),
+           py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_seqlens"),
+           py::arg("max_seqlen"), py::arg("causal"), py::arg("dropout"), py::arg("seed"),
+           py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"));
 
   auto dn = m.def_submodule("dense", "dense-layer bias gradients / fused GELU backward");
   dn.def("bias_grad", &bias_grad_op);

@@ -6,6 +6,7 @@
     python tools/microbench.py optim   # optimizer step bandwidth (ResNet-50 sizes)
     python tools/microbench.py ln      # FusedLayerNorm fwd/bwd vs torch LayerNorm
     python tools/microbench.py lamb    # FusedLAMB / FusedAdam on BERT-large's 336M params
+    python tools/microbench.py attn-packed  # packed (cu_seqlens) vs padded + key mask attention
 """
 from __future__ import annotations
 
@@ -550,6 +551,61 @@ def bench_attn(args):
             print("%-8s %-12s fwd %.0f us (%.0f TF)  bwd %.0f us (%.0f TF)" % (
                 lib, name, tf_, fl / (tf_ * 1e-6) / 1e12, tb, 2.5 * fl / (tb * 1e-6) / 1e12),
                 flush=True)
+    bench_attn_packed(args)
+
+
+def bench_attn_packed(args):
+    """Packed variable-length attention (fwd_varlen / bwd_varlen on the real tokens) against
+    the padded [32, 512] call with the equivalent key-padding mask: B = 32 sequences with
+    lengths drawn once (seed 0) uniformly from [64, 512], H = 16, bf16, forward + backward.
+    The two are timed alternately, three rounds each; the share of real (query, key) pairs
+    is what the packed time would be of the padded one if time followed the pairs alone."""
+    from apex_example_amd import _native
+
+    dev, dt, B, S, H, d = "cuda", torch.bfloat16, 32, 512, 16, 64
+    A = _native.require().attn
+    g = torch.Generator().manual_seed(0)
+    lens = torch.randint(64, S + 1, (B,), generator=g)
+    T, sc = int(lens.sum()), 1.0 / d ** 0.5
+    pairs = float((lens.double() ** 2).sum()) / (B * S * S)
+    print("lengths %s" % lens.tolist())
+    print("T = %d of %d tokens (%.3f), real (query, key) pairs %.3f of the padded batch's" % (
+        T, B * S, T / (B * S), pairs))
+    cu = torch.nn.functional.pad(lens.cumsum(0), (1, 0)).to(torch.int32).to(dev)
+    gone = (torch.arange(S).view(1, S) >= lens.view(B, 1)).to(dev)
+    kb, kl = A.prepare_key_mask(gone, S)   # once per forward for all layers: not timed
+    pq, pk, pv, pdo = (torch.randn(B, S, H, d, device=dev, dtype=dt) for _ in range(4))
+    keep = (~gone).reshape(-1).nonzero().squeeze(1)
+    q, k, v, do = (t.reshape(B * S, H, d).index_select(0, keep) for t in (pq, pk, pv, pdo))
+    pg = [torch.empty_like(pq) for _ in range(3)]
+    vg = [torch.empty_like(q) for _ in range(3)]
+    for p in (0.0, 0.1):
+        po, plse = A.fwd(pq, pk, pv, False, p, 1234, sc, kb, kl)
+        o, lse = A.fwd_varlen(q, k, v, cu, S, False, p, 1234, sc)
+        calls = {
+            "padded fwd": lambda: A.fwd(pq, pk, pv, False, p, 1234, sc, kb, kl),
+            "packed fwd": lambda: A.fwd_varlen(q, k, v, cu, S, False, p, 1234, sc),
+            "padded bwd": lambda: A.bwd(pdo, pq, pk, pv, po, plse, False, p, 1234, sc, *pg, kb,
+                                        kl),
+            "packed bwd": lambda: A.bwd_varlen(do, q, k, v, o, lse, cu, S, False, p, 1234, sc,
+                                               *vg),
+        }
+        t_end = time.time() + 2.0   # untimed first (clock / first-use ramp, see bench_attn)
+        while time.time() < t_end:
+            for f in calls.values():
+                f()
+            torch.cuda.synchronize()
+        times = {n: [] for n in calls}
+        for _ in range(3):
+            for n, f in calls.items():
+                times[n].append(timeit(f, iters=100, warmup=10))
+        best = {n: min(ts) for n, ts in times.items()}
+        for n, ts in times.items():
+            print("p=%.1f %s: %s us" % (p, n, " ".join("%.0f" % t for t in ts)), flush=True)
+        pad_t = best["padded fwd"] + best["padded bwd"]
+        pack_t = best["packed fwd"] + best["packed bwd"]
+        print("p=%.1f fwd+bwd padded %.0f us, packed %.0f us: %.3f of padded (pairs %.3f)" % (
+            p, pad_t, pack_t, pack_t / pad_t, pairs), flush=True)
 
 
 def bench_optim(args):
@@ -812,11 +868,12 @@ def bench_conv1x1_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
-                             "attn"])
+                             "attn", "attn-packed"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
-     "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn}[a.what](a)
+     "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn,
+     "attn-packed": bench_attn_packed}[a.what](a)
 
 
 if __name__ == "__main__":
