@@ -4,7 +4,7 @@ buffer, ``cu_seqlens`` (int32 [B + 1]) gives each sequence's first row, and atte
 per sequence inside the gfx950 fused attention kernels (``ops.attention``'s
 ``fused_attention_varlen_qkv``: no padded query, key or output row exists anywhere).
 
-Off the fused path (CPU, fp32, head dim != 64) a per-sequence
+Off the fused path (CPU, fp32, head dim other than 64 or 128) a per-sequence
 ``F.scaled_dot_product_attention`` loop over ``cu_seqlens`` gives the same result."""
 from __future__ import annotations
 

@@ -47,7 +47,7 @@ def _fused_key_mask(key_padding_mask, mask_additive, device):
 def attention_bshd(q, k, v, dropout_p, key_padding_mask=None, attn_mask=None,
                    mask_additive=False, allow_fused=True, kv=None):
     """q [B, Tq, H, D], k/v [B, Tk, H, D] (any strides) -> [B, Tq, H, D].
-    gfx950 fused kernels when eligible (no attn_mask, D == 64, 16-bit; Tq and Tk may
+    gfx950 fused kernels when eligible (no attn_mask, D 64 or 128, 16-bit; Tq and Tk may
     differ; a key-padding mask [B, Tk] - boolean / byte, or additive under
     ``mask_additive``, or an ops.attention.PreparedKeyMask - is applied inside the
     kernels), PyTorch SDPA otherwise.  ``kv``: the packed [B, Tk, 2, H, D] tensor that k

@@ -4,7 +4,7 @@ SURVEY.md A-24): time-first encoder-decoder attention, queries from ``query``
 (fused ``in_proj_weight_kv``), optional fused pre-LayerNorm + residual add.
 The gfx950 fused attention kernels (``ops.fused_attention_kv`` on the packed kv
 projection) run for any Tq and Tk, with or without a key-padding mask [B, Tk]
-(head dim 64, bf16 / fp16, ``impl="fast"``); an ``attn_mask`` [Tq, Tk] goes to PyTorch
+(head dim 64 or 128, bf16 / fp16, ``impl="fast"``); an ``attn_mask`` [Tq, Tk] goes to PyTorch
 SDPA.
 """
 from __future__ import annotations

@@ -185,8 +185,10 @@ class BertModel(nn.Module):
             # [b, s] 1 = keep -> additive [b, 1, 1, s]
             mask = additive_attention_mask(attention_mask, x.dtype)[:, None, None, :]
             head_dim = self.config.hidden_size // self.config.num_attention_heads
-            if (self.config.fused_attention and x.is_cuda and head_dim == 64
-                    and _native.available()):
+            # supported() minus its dtype test: under autocast x is fp32 here while each
+            # layer's qkv is 16-bit, and it is the layer that asks supported(qkv, d)
+            if (self.config.fused_attention and x.is_cuda
+                    and head_dim in fused_attn.HEAD_DIMS and _native.available()):
                 # the same -10000 bias (never -inf: no row is fully masked), prepared once
                 # for the fused kernels of all layers (each layer takes them when its qkv
                 # is 16-bit, the SDPA path with `mask` otherwise)

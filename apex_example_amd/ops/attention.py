@@ -1,20 +1,20 @@
-"""Fused multi-head attention (head dim 64, bf16 / fp16) on the gfx950 MFMA
-kernels of csrc/hip/attention.hip: flash-attention style forward (online
-softmax, never materialises the S x S scores) and backward (dK/dV and dQ
+"""Fused multi-head attention (head dim D = 64 or 128, bf16 / fp16) on the gfx950 MFMA
+kernels of csrc/hip/attention.hip (D = 64) and csrc/hip/attention_d128.hip (D = 128):
+flash-attention style forward (online softmax, never materialises the S x S scores) and backward (dK/dV and dQ
 kernels recomputing P from the saved log-sum-exp; no atomics, so gradients are
 bitwise reproducible), with an optional causal mask and dropout whose keep
 mask is a counter-based hash of (seed, batch*head, query, key) regenerated
 exactly by the backward.
 
-``fused_attention_qkv(qkv)`` takes the packed [B, S, 3, H, 64] output of a
-fused QKV projection and returns o as [B, S, H, 64] (``.view(B, S, H*64)`` is
+``fused_attention_qkv(qkv)`` takes the packed [B, S, 3, H, D] output of a
+fused QKV projection and returns o as [B, S, H, D] (``.view(B, S, H*D)`` is
 free); its backward writes dQ/dK/dV straight into ONE packed buffer, so the
 projection's input gradient needs no concatenation.  Layout-generic views
 ([S, B, ...] sequence-first included) work: the kernels take strides.
 
-Cross-attention: q may be [B, Sq, H, 64] against k / v of another length
-[B, Sk, H, 64] (``fused_attention``), and ``fused_attention_kv(q, kv)`` takes the packed
-[B, Sk, 2, H, 64] output of a fused KV projection, its backward writing dK/dV into ONE
+Cross-attention: q may be [B, Sq, H, D] against k / v of another length
+[B, Sk, H, D] (``fused_attention``), and ``fused_attention_kv(q, kv)`` takes the packed
+[B, Sk, 2, H, D] output of a fused KV projection, its backward writing dK/dV into ONE
 packed buffer of kv's layout.  The causal mask is defined for Sq == Sk only.
 
 Key masks: ``key_padding_mask`` ([B, S] bool with S the KEY length, True = masked key,
@@ -28,18 +28,18 @@ get exactly zero dK / dV, and a query whose keys are all masked gets o = 0 and
 dq = 0 (its lse is unspecified) instead of NaN.
 
 Packed variable-length sequences: ``fused_attention_varlen(q, k, v, cu_seqlens)`` takes
-[T, H, 64] views holding only the real tokens of B sequences, sequence b owning rows
+[T, H, D] views holding only the real tokens of B sequences, sequence b owning rows
 ``cu_seqlens[b] .. cu_seqlens[b+1]-1`` (int32 [B + 1] on the GPU, read by the kernels), and
 attends within each sequence (``causal`` per sequence): no padded query, key or token-wise
-work around the attention.  ``fused_attention_varlen_qkv`` takes the packed [T, 3, H, 64]
+work around the attention.  ``fused_attention_varlen_qkv`` takes the packed [T, 3, H, D]
 output of a fused QKV projection and returns one dqkv of its layout.  The results are
 those of the padded call with a key-padding mask, read at the real rows; not combined
 with key masks or unequal query / key lengths.
 
-Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64, q and k / v of one
+Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size and head count (the query and key lengths may differ), no mask other than
 a per-batch key mask (a [Tq, Tk] ``attn_mask`` is not fused) or, at equal lengths, the
-causal mask; packed sequences ([T, H, 64] with ``cu_seqlens``): q, k and v of one token
+causal mask; packed sequences ([T, H, D] with ``cu_seqlens``): q, k and v of one token
 and head count, self-attention per sequence, optional causal mask, no key mask.  Callers
 fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
@@ -56,8 +56,11 @@ def _C():
     return _native.require().attn
 
 
+HEAD_DIMS = (64, 128)  # the head dims that have kernels
+
+
 def supported(t: torch.Tensor, head_dim: int) -> bool:
-    return (t.is_cuda and head_dim == 64 and t.dtype in (torch.bfloat16, torch.float16)
+    return (t.is_cuda and head_dim in HEAD_DIMS and t.dtype in (torch.bfloat16, torch.float16)
             and _native.available())
 
 
@@ -154,24 +157,24 @@ def _check_causal(causal, Sq, Sk):
                          "Sk = %d" % (Sq, Sk))
 
 
-# How a call's tensor inputs split into the q [B, Sq, H, 64] and k, v [B, Sk, H, 64] views
-# the kernels take (packed variable-length layouts: [T, H, 64] views); the gradient
+# How a call's tensor inputs split into the q [B, Sq, H, D] and k, v [B, Sk, H, D] views
+# the kernels take (packed variable-length layouts: [T, H, D] views); the gradient
 # buffers, one per input, split the same way.
 _SPLIT = {
     "qkv": lambda ts: ts,                                # q, k, v
-    "packed_qkv": lambda ts: ts[0].unbind(2),            # qkv [B, S, 3, H, 64]
-    "q_packed_kv": lambda ts: (ts[0], *ts[1].unbind(2)),  # q, kv [B, Sk, 2, H, 64]
-    "varlen_qkv": lambda ts: ts,                         # q, k, v [T, H, 64]
-    "varlen_packed_qkv": lambda ts: ts[0].unbind(1),     # qkv [T, 3, H, 64]
+    "packed_qkv": lambda ts: ts[0].unbind(2),            # qkv [B, S, 3, H, D]
+    "q_packed_kv": lambda ts: (ts[0], *ts[1].unbind(2)),  # q, kv [B, Sk, 2, H, D]
+    "varlen_qkv": lambda ts: ts,                         # q, k, v [T, H, D]
+    "varlen_packed_qkv": lambda ts: ts[0].unbind(1),     # qkv [T, 3, H, D]
 }
 
 
 class AttentionFunction(torch.autograd.Function):
-    """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v -> [B, Sq, H, 64]
+    """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v -> [B, Sq, H, D]
     on the q / k / v views of ``inputs`` (any strides) under ``layout``, a key of ``_SPLIT``;
     (kbias, klive) is a prepared key mask of the Sk keys or (None, None).  ``varlen`` is
-    None or, with the "varlen_*" layouts ([T, H, 64] views of packed sequences, o
-    [T, H, 64]), the pair (cu_seqlens int32 [B + 1], max_seqlen); it rides in ``ctx``
+    None or, with the "varlen_*" layouts ([T, H, D] views of packed sequences, o
+    [T, H, D]), the pair (cu_seqlens int32 [B + 1], max_seqlen); it rides in ``ctx``
     outside autograd's saved tensors, so a captured graph may be replayed on new offsets
     written into the same tensor.  The backward
     returns one gradient per input: packed inputs (and the q beside a packed kv: a
@@ -231,7 +234,7 @@ class FusedKVAttentionFunction:
 
 def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
                     key_bias=None):
-    """q: [B, Sq, H, 64], k, v: [B, Sk, H, 64] -> o [B, Sq, H, 64] (Sq != Sk is
+    """q: [B, Sq, H, D], k, v: [B, Sk, H, D] -> o [B, Sq, H, D] (Sq != Sk is
     cross-attention; ``causal`` needs Sq == Sk).  key_padding_mask: [B, Sk] bool, True =
     masked key; key_bias: [B, Sk] float, added to the scaled scores; either may be a
     ``PreparedKeyMask``."""
@@ -243,11 +246,11 @@ def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_paddin
 
 
 def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, key_bias=None):
-    """q: [B, Sq, H, 64], kv: [B, Sk, 2, H, 64] (the packed output of a fused KV
-    projection, any strides) -> o [B, Sq, H, 64]; the backward writes dK and dV into one
+    """q: [B, Sq, H, D], kv: [B, Sk, 2, H, D] (the packed output of a fused KV
+    projection, any strides) -> o [B, Sq, H, D]; the backward writes dK and dV into one
     packed dkv of kv's layout.  Masks are [B, Sk], as in ``fused_attention``."""
     if kv.dim() != 5 or kv.size(2) != 2:
-        raise ValueError("kv must be [B, Sk, 2, H, 64], got %s" % (tuple(kv.shape),))
+        raise ValueError("kv must be [B, Sk, 2, H, D], got %s" % (tuple(kv.shape),))
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
     kbias, klive = _key_mask(key_padding_mask, key_bias, kv)
     return FusedKVAttentionFunction.apply(q, kv, dropout_p, scale, _seed(dropout_p),
@@ -256,7 +259,7 @@ def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, 
 
 def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
                         key_bias=None):
-    """qkv: [B, S, 3, H, 64] (any strides) -> o [B, S, H, 64]; the backward returns one
+    """qkv: [B, S, 3, H, D] (any strides) -> o [B, S, H, D]; the backward returns one
     packed dqkv of qkv's layout.  Masks as in ``fused_attention``."""
     scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
     kbias, klive = _key_mask(key_padding_mask, key_bias, qkv)
@@ -298,11 +301,11 @@ def _varlen(cu_seqlens, max_seqlen, like, key_padding_mask, key_bias):
 
 def fused_attention_varlen(q, k, v, cu_seqlens, max_seqlen=None, causal=False, dropout_p=0.0,
                            scale=None, key_padding_mask=None, key_bias=None):
-    """Attention over packed variable-length sequences.  q, k, v: [T, H, 64] views (any
+    """Attention over packed variable-length sequences.  q, k, v: [T, H, D] views (any
     token / head strides) of the real tokens of B sequences; cu_seqlens: int32 [B + 1] on
     the GPU, non-decreasing from 0 to T: sequence b owns rows cu[b] .. cu[b+1]-1, and its
     queries see its own keys only (``causal``: key j <= query i, indices local to the
-    sequence).  -> o [T, H, 64], equal to the padded call with a key-padding mask read at
+    sequence).  -> o [T, H, D], equal to the padded call with a key-padding mask read at
     the real rows (same dropout mask for the same seed).  Empty sequences are legal.
 
     max_seqlen=None: computed from cu_seqlens with ONE host sync, which also checks the
@@ -322,11 +325,11 @@ def fused_attention_varlen(q, k, v, cu_seqlens, max_seqlen=None, causal=False, d
 
 def fused_attention_varlen_qkv(qkv, cu_seqlens, max_seqlen=None, causal=False, dropout_p=0.0,
                                scale=None, key_padding_mask=None, key_bias=None):
-    """qkv: [T, 3, H, 64] (the packed output of a fused QKV projection over packed
-    sequences, any strides) -> o [T, H, 64]; the backward returns one packed dqkv of qkv's
+    """qkv: [T, 3, H, D] (the packed output of a fused QKV projection over packed
+    sequences, any strides) -> o [T, H, D]; the backward returns one packed dqkv of qkv's
     layout.  cu_seqlens / max_seqlen as in ``fused_attention_varlen``."""
     if qkv.dim() != 4 or qkv.size(1) != 3:
-        raise ValueError("qkv must be [T, 3, H, 64], got %s" % (tuple(qkv.shape),))
+        raise ValueError("qkv must be [T, 3, H, D], got %s" % (tuple(qkv.shape),))
     cu_seqlens, max_seqlen = _varlen(cu_seqlens, max_seqlen, qkv, key_padding_mask, key_bias)
     scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
     return AttentionFunction.apply("varlen_packed_qkv", causal, dropout_p, scale,

@@ -498,15 +498,16 @@ void gelu_fwd(const void* x, void* y, DType t, int64_t n, bool tanh_approx, hipS
 void colsum(const void* x, const void* pre, void* out_dpre, DType t, int64_t M, int N,
             int act_mode, float* part, int S, void* bias_grad, DType tb, hipStream_t st);
 
-// ---- fused attention, head dim 64 (attention.hip) ---------------------------
-// A [B, S, H, 64] tensor with a contiguous head dim: pointer and element strides.
+// ---- fused attention, head dim D = 64 (attention.hip) or 128 (attention_d128.hip) ----
+// A [B, S, H, D] tensor with a contiguous head dim: pointer and element strides.
 struct AttnView {
   void* p = nullptr;
   int64_t sb = 0, ss = 0, sh = 0;  // batch, sequence, head
 };
 // One attention problem, shared by the forward and the backward.
 struct AttnProblem {
-  AttnView q, k, v;  // q [B,Sq,H,64], k / v [B,Sk,H,64]
+  AttnView q, k, v;  // q [B,Sq,H,D], k / v [B,Sk,H,D]
+  int D = 64;        // head dim: 64 or 128 (attn_fwd / attn_bwd abort on anything else)
   int B, H;
   int Sq, Sk;        // query / key length, both > 0 at a launch
   float scale, dropout;
@@ -517,7 +518,7 @@ struct AttnProblem {
   const float* kbias = nullptr;          // [B][attn_lse_stride(Sk)]
   const unsigned char* klive = nullptr;  // [B][attn_lse_stride(Sk) / 64]
   // Packed variable-length sequences: when set, q / k / v (and the backward's o, dout, dq,
-  // dk, dv) are [T, H, 64] views (sb unused, ss = the token stride), sequence b owns rows
+  // dk, dv) are [T, H, D] views (sb unused, ss = the token stride), sequence b owns rows
   // cu_seqlens[b] .. cu_seqlens[b + 1] - 1 and attends within itself, B is the number of
   // sequences and Sq = Sk = max_seqlen >= every length (it sizes the grid and the lse
   // rows; results do not depend on it).  int32 [B + 1] on the device, read by the kernels
@@ -528,7 +529,7 @@ struct AttnProblem {
 // Row stride of lse / D (S = Sq) and of the prepared key mask (S = Sk): S rounded up to
 // a multiple of 64.
 int attn_lse_stride(int S);
-// o [B][Sq][H][64] contiguous, lse [B][H][attn_lse_stride(Sq)]
+// o [B][Sq][H][D] contiguous, lse [B][H][attn_lse_stride(Sq)]
 void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st);
 
 // Per-batch key mask [B][S] -> the prepared pair the attention kernels read: an fp32

@@ -1,4 +1,5 @@
-// Torch bindings for the fused attention kernels (csrc/hip/attention.hip).
+// Torch bindings for the fused attention kernels (csrc/hip/attention.hip at head dim 64,
+// csrc/hip/attention_d128.hip at 128).
 #include "attn_ops.h"
 
 #include <limits>
@@ -14,10 +15,13 @@ bool view_ok(const at::Tensor& t) {
          t.stride(1) % 8 == 0 && t.stride(2) % 8 == 0;
 }
 
-// the kernels' view of a [B,S,H,64] tensor, or the reason it has none
+// the head dims that have kernels
+bool head_dim_ok(int64_t D) { return D == 64 || D == 128; }
+
+// the kernels' view of a [B,S,H,D] tensor (D = 64 or 128), or the reason it has none
 AttnView view_of(const at::Tensor& t, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.size(3) == 64, "attn: ", what,
-              " must be a [B,S,H,64] GPU tensor");
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && head_dim_ok(t.size(3)), "attn: ", what,
+              " must be a [B,S,H,64] or [B,S,H,128] GPU tensor, got ", t.sizes());
   TORCH_CHECK(t.stride(3) == 1, "attn: ", what, ": head dim must be contiguous");
   TORCH_CHECK(view_ok(t), "attn: ", what, ": 16-byte aligned rows required");
   // the kernels' tile DMA uses 32-bit per-lane row offsets (csrc/hip/attention.hip)
@@ -26,7 +30,7 @@ AttnView view_of(const at::Tensor& t, const char* what) {
   return {t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)};
 }
 
-// q [B, Sq, H, 64], k / v [B, Sk, H, 64]: one B, H and dtype, any strides
+// q [B, Sq, H, D], k / v [B, Sk, H, D]: one B, H, D and dtype, any strides
 AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                         bool causal, double dropout, int64_t seed, double scale) {
   AttnProblem L;
@@ -35,9 +39,9 @@ AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tens
   L.v = view_of(v, "v");
   TORCH_CHECK(v.sizes() == k.sizes(), "attn: k and v shapes differ: ", k.sizes(), " and ",
               v.sizes());
-  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2),
-              "attn: q and k / v differ in batch or heads: q ", q.sizes(), ", k ", k.sizes(),
-              " (only the sequence length may differ)");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3),
+              "attn: q and k / v differ in batch or heads (or head dim): q ", q.sizes(), ", k ",
+              k.sizes(), " (only the sequence length may differ)");
   TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type() &&
                   (q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf),
               "attn: bf16/fp16 q,k,v of one dtype");
@@ -48,6 +52,7 @@ AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tens
               q.size(1), ", Sk = ", k.size(1));
   TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "attn: dropout must be in [0, 1)");
   L.B = (int)q.size(0); L.Sq = (int)q.size(1); L.Sk = (int)k.size(1); L.H = (int)q.size(2);
+  L.D = (int)q.size(3);
   L.scale = (float)scale; L.dropout = (float)dropout; L.seed = (uint32_t)seed;
   L.causal = causal; L.dtype = dtype_of(q);
   return L;
@@ -82,16 +87,16 @@ void check_key_mask(const c10::optional<at::Tensor>& bias, const c10::optional<a
   *pl = kl.data_ptr<unsigned char>();
 }
 
-// ---- packed variable-length sequences: [T, H, 64] views and an int32 offsets vector
+// ---- packed variable-length sequences: [T, H, D] views and an int32 offsets vector
 bool view3_ok(const at::Tensor& t) {
   return t.stride(2) == 1 && ((uintptr_t)t.data_ptr() % 16) == 0 && t.stride(0) % 8 == 0 &&
          t.stride(1) % 8 == 0;
 }
 
-// the kernels' view of a packed [T,H,64] tensor (no batch stride), or the reason it has none
+// the kernels' view of a packed [T,H,D] tensor (no batch stride), or the reason it has none
 AttnView view3_of(const at::Tensor& t, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.dim() == 3 && t.size(2) == 64, "attn varlen: ", what,
-              " must be a [T,H,64] GPU tensor");
+  TORCH_CHECK(t.is_cuda() && t.dim() == 3 && head_dim_ok(t.size(2)), "attn varlen: ", what,
+              " must be a [T,H,64] or [T,H,128] GPU tensor, got ", t.sizes());
   TORCH_CHECK(t.stride(2) == 1, "attn varlen: ", what, ": head dim must be contiguous");
   TORCH_CHECK(view3_ok(t), "attn varlen: ", what, ": 16-byte aligned rows required");
   TORCH_CHECK(t.stride(0) >= 0 && t.stride(0) < (int64_t{1} << 24), "attn varlen: ", what,
@@ -99,7 +104,7 @@ AttnView view3_of(const at::Tensor& t, const char* what) {
   return {t.data_ptr(), 0, t.stride(0), t.stride(1)};
 }
 
-// q, k, v [T, H, 64] of one T, H and dtype, any token / head strides; cu_seqlens int32
+// q, k, v [T, H, D] of one T, H, D and dtype, any token / head strides; cu_seqlens int32
 // [B + 1] on q's device; Sq = Sk = max_seqlen
 AttnProblem make_varlen_launch(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                const at::Tensor& cu, int64_t max_seqlen, bool causal,
@@ -109,7 +114,7 @@ AttnProblem make_varlen_launch(const at::Tensor& q, const at::Tensor& k, const a
   L.k = view3_of(k, "k");
   L.v = view3_of(v, "v");
   TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(),
-              "attn varlen: q, k and v differ in tokens or heads: q ", q.sizes(), ", k ",
+              "attn varlen: q, k and v differ in tokens or heads (or head dim): q ", q.sizes(), ", k ",
               k.sizes(), ", v ", v.sizes());
   TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type() &&
                   (q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf),
@@ -126,7 +131,7 @@ AttnProblem make_varlen_launch(const at::Tensor& q, const at::Tensor& k, const a
               "attn varlen: max_seqlen must be in (0, 2^24), got ", max_seqlen);
   TORCH_CHECK(q.size(0) < (int64_t{1} << 31), "attn varlen: too many tokens: ", q.size(0));
   TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "attn: dropout must be in [0, 1)");
-  L.B = (int)cu.size(0) - 1; L.H = (int)q.size(1);
+  L.B = (int)cu.size(0) - 1; L.H = (int)q.size(1); L.D = (int)q.size(2);
   TORCH_CHECK((int64_t)L.B * L.H <= 65535, "attn varlen: sequences x heads = ",
               (int64_t)L.B * L.H, " exceeds the 65535 rows of a launch grid");
   L.Sq = L.Sk = (int)max_seqlen;
@@ -174,7 +179,7 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
   AttnProblem L = make_launch(q, k, v, causal, dropout, seed, scale);
   check_key_mask(key_bias, key_live, q, L.B, L.Sk, &L.kbias, &L.klive);
   const int Sp = attn_lse_stride(L.Sq);
-  at::Tensor o = at::empty({L.B, L.Sq, L.H, 64}, q.options());
+  at::Tensor o = at::empty({L.B, L.Sq, L.H, L.D}, q.options());
   at::Tensor lse = at::empty({L.B, L.H, Sp}, q.options().dtype(at::kFloat));
   if (L.Sk == 0) {  // no key to attend to: o = 0, lse = log2(0), no launch
     o.zero_();
@@ -246,7 +251,7 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_varlen_op(at::Tensor q, at::Tensor k
   c10::NoGradGuard no_grad_;
   AttnProblem L = make_varlen_launch(q, k, v, cu_seqlens, max_seqlen, causal, dropout, seed, scale);
   const int Sp = attn_lse_stride(L.Sq);
-  at::Tensor o = at::empty({L.T, L.H, 64}, q.options());
+  at::Tensor o = at::empty({L.T, L.H, L.D}, q.options());
   at::Tensor lse = at::empty({L.B, L.H, Sp}, q.options().dtype(at::kFloat));
   if (L.B == 0) o.zero_();  // no sequence owns any row
   else if (L.T > 0 && L.H > 0) attn_fwd(L, o.data_ptr(), lse.data_ptr<float>(), cur_stream());

@@ -100,7 +100,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ln.def("set_bwd_one_row", &layer_norm_bwd_one_row);
   ln.def("bwd_one_row", &layer_norm_bwd_one_row_on);
 
-  auto attn = m.def_submodule("attn", "fused attention (head dim 64, MFMA, gfx950)");
+  auto attn = m.def_submodule("attn", "fused attention (head dim 64 or 128, MFMA, gfx950)");
   attn.def("fwd", &attn_fwd_op, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
            py::arg("dropout"), py::arg("seed"), py::arg("scale"),
            py::arg("key_bias") = py::none(), py::arg("key_live") = py::none());

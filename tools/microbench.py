@@ -552,6 +552,72 @@ def bench_attn(args):
                 lib, name, tf_, fl / (tf_ * 1e-6) / 1e12, tb, 2.5 * fl / (tb * 1e-6) / 1e12),
                 flush=True)
     bench_attn_packed(args)
+    bench_attn_d128(args)
+
+
+def bench_attn_d128(args):
+    """Head dim 128 (csrc/hip/attention_d128.hip) against F.scaled_dot_product_attention,
+    which served these shapes before: bf16 forward and backward of the native calls and of
+    each available SDPA flash backend, timed alternately in one process over ROUNDS rounds.  Prints
+    each variant's median and its spread over the rounds, (max - min) / median."""
+    from apex_example_amd import _native
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    A = _native.require().attn
+    libs = []
+    for lib in ("default", "ck"):
+        try:
+            torch.backends.cuda.preferred_rocm_fa_library(lib)
+            libs.append(lib)
+        except Exception as e:  # noqa: BLE001
+            print("backend %s unavailable: %s" % (lib, e))
+    print("| shape (B x H x S, D = 128) | variant | fwd us | bwd us | fwd + bwd us | spread | TF |")
+    print("|---|---|---|---|---|---|---|")
+    for name, b, h, s_, causal in [("8 x 16 x 1024 causal", 8, 16, 1024, True),
+                                   ("4 x 16 x 2048", 4, 16, 2048, False)]:
+        d, sc = 128, 1.0 / 128 ** 0.5
+        q, k, v, do = (torch.randn(b, s_, h, d, device=dev, dtype=dt) for _ in range(4))
+        dq, dk, dv = (torch.empty_like(t) for t in (q, k, v))
+        o, lse = A.fwd(q, k, v, causal, 0.0, 0, sc)
+        # SDPA takes [B, H, S, D]; contiguous copies, so neither side pays for a layout
+        sq, sk, sv = (t.transpose(1, 2).contiguous().requires_grad_(True) for t in (q, k, v))
+        sdo = do.transpose(1, 2).contiguous()
+
+        def native():
+            return (lambda: A.fwd(q, k, v, causal, 0.0, 0, sc),
+                    lambda: A.bwd(do, q, k, v, o, lse, causal, 0.0, 0, sc, dq, dk, dv))
+
+        def sdpa(lib):
+            torch.backends.cuda.preferred_rocm_fa_library(lib)
+            f = lambda: F.scaled_dot_product_attention(sq, sk, sv, is_causal=causal)  # noqa: E731
+            so = f()
+            return f, lambda: torch.autograd.grad(so, (sq, sk, sv), sdo, retain_graph=True)
+
+        variants = [("gfx950 native", native)] + [("sdpa " + lib, lambda lib=lib: sdpa(lib))
+                                                  for lib in libs]
+        t_end = time.time() + 2.0  # clock / first-use ramp, as in bench_attn
+        while time.time() < t_end:
+            for fn in native():
+                fn()
+            torch.cuda.synchronize()
+        times = {n: [] for n, _ in variants}
+        for _ in range(ROUNDS):
+            for n, make in variants:
+                try:
+                    f, bw = make()
+                    times[n].append((timeit(f, iters=30, warmup=5), timeit(bw, iters=30, warmup=5)))
+                except Exception as e:  # noqa: BLE001
+                    print("%s %s failed: %s" % (n, name, str(e)[:200]))
+        fl = 3.5 * 4 * b * h * s_ * s_ * d * (0.5 if causal else 1.0)
+        med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+        for n, _ in variants:
+            if len(times[n]) < ROUNDS:
+                continue
+            tot = [tf_ + tb for tf_, tb in times[n]]
+            print("| %s | %s | %.0f | %.0f | %.0f | %.1f %% | %.0f |" % (
+                name, n, med([tf_ for tf_, _ in times[n]]), med([tb for _, tb in times[n]]),
+                med(tot), 100 * (max(tot) - min(tot)) / med(tot), fl / (med(tot) * 1e-6) / 1e12),
+                flush=True)
 
 
 def bench_attn_packed(args):
@@ -868,12 +934,12 @@ def bench_conv1x1_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
-                             "attn", "attn-packed"])
+                             "attn", "attn-packed", "attn-d128"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
      "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn,
-     "attn-packed": bench_attn_packed}[a.what](a)
+     "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128}[a.what](a)
 
 
 if __name__ == "__main__":
