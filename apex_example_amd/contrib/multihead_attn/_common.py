@@ -44,17 +44,41 @@ def _fused_key_mask(key_padding_mask, mask_additive, device):
     return {"key_padding_mask": kp.bool()}
 
 
+def _fused_pair_mask(attn_mask, key_padding_mask, mask_additive, device):
+    """The fused ops' keyword arguments for a boolean / byte ``attn_mask`` (with the
+    boolean key-padding mask the prepare step merges), or None where the masks are not of
+    that kind (additive, floating, a prepared key mask)."""
+    def boolean(m):
+        return isinstance(m, torch.Tensor) and m.dtype in (torch.bool, torch.uint8)
+    if mask_additive or not boolean(attn_mask) or attn_mask.dim() != 2:
+        return None
+    if key_padding_mask is not None and not boolean(key_padding_mask):
+        return None
+    kw = {"attn_mask": attn_mask.to(device)}
+    if key_padding_mask is not None:
+        kw["key_padding_mask"] = key_padding_mask.to(device).bool()
+    return kw
+
+
 def attention_bshd(q, k, v, dropout_p, key_padding_mask=None, attn_mask=None,
-                   mask_additive=False, allow_fused=True, kv=None):
+                   mask_additive=False, allow_fused=True, kv=None, fused_attn_mask=False):
     """q [B, Tq, H, D], k/v [B, Tk, H, D] (any strides) -> [B, Tq, H, D].
     gfx950 fused kernels when eligible (no attn_mask, D 64 or 128, 16-bit; Tq and Tk may
     differ; a key-padding mask [B, Tk] - boolean / byte, or additive under
     ``mask_additive``, or an ops.attention.PreparedKeyMask - is applied inside the
     kernels), PyTorch SDPA otherwise.  ``kv``: the packed [B, Tk, 2, H, D] tensor that k
     and v are the two halves of, when there is one: the fused path then takes it whole
-    (``fused_attention_kv``: one packed dkv in the backward); the SDPA path uses k and v."""
+    (``fused_attention_kv``: one packed dkv in the backward); the SDPA path uses k and v.
+    ``fused_attn_mask``: a boolean / byte ``attn_mask`` [Tq, Tk] goes to the fused kernels
+    too (bit tiles, ops.attention.prepare_attn_mask); off, every ``attn_mask`` takes SDPA."""
     B, Tq, H, D = q.shape
     Tk = k.size(1)
+    if allow_fused and fused_attn_mask and attn_mask is not None and fused_attn.supported(q, D):
+        mask_kw = _fused_pair_mask(attn_mask, key_padding_mask, mask_additive, q.device)
+        if mask_kw is not None:
+            if kv is not None:
+                return fused_attn.fused_attention_kv(q, kv, dropout_p=dropout_p, **mask_kw)
+            return fused_attn.fused_attention(q, k, v, dropout_p=dropout_p, **mask_kw)
     if allow_fused and attn_mask is None and fused_attn.supported(q, D):
         mask_kw = _fused_key_mask(key_padding_mask, mask_additive, q.device)
         if kv is not None:

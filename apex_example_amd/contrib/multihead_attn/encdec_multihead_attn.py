@@ -5,7 +5,7 @@ SURVEY.md A-24): time-first encoder-decoder attention, queries from ``query``
 The gfx950 fused attention kernels (``ops.fused_attention_kv`` on the packed kv
 projection) run for any Tq and Tk, with or without a key-padding mask [B, Tk]
 (head dim 64 or 128, bf16 / fp16, ``impl="fast"``); an ``attn_mask`` [Tq, Tk] goes to PyTorch
-SDPA.
+SDPA, or, boolean and with ``fused_attn_mask=True``, to the fused kernels as bit tiles.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ from ._common import attention_bshd
 
 class EncdecMultiheadAttn(nn.Module):
     def __init__(self, embed_dim, num_heads, dropout=0.0, bias=False, include_norm_add=False,
-                 impl="fast"):
+                 impl="fast", fused_attn_mask=False):
         super().__init__()
         self.embed_dim = embed_dim
         self.num_heads = num_heads
@@ -31,6 +31,8 @@ class EncdecMultiheadAttn(nn.Module):
         self.bias = bias
         self.include_norm_add = include_norm_add
         self.impl = impl
+        # a boolean attn_mask goes to the fused kernels (bit tiles) instead of SDPA
+        self.fused_attn_mask = fused_attn_mask
         self.scaling = self.head_dim ** -0.5
         self.in_proj_weight_q = Parameter(torch.empty(embed_dim, embed_dim))
         self.in_proj_weight_kv = Parameter(torch.empty(2 * embed_dim, embed_dim))
@@ -74,7 +76,8 @@ class EncdecMultiheadAttn(nn.Module):
         k, v = kv.unbind(2)
         p = self.dropout if (is_training and self.training) else 0.0
         o = attention_bshd(q, k, v, p, key_padding_mask, attn_mask, False,
-                           allow_fused=(self.impl == "fast"), kv=kv)
+                           allow_fused=(self.impl == "fast"), kv=kv,
+                           fused_attn_mask=self.fused_attn_mask)
         out = F.linear(o.transpose(0, 1).reshape(Tq, B, E), self.out_proj_weight,
                        self.out_proj_bias)
         if self.include_norm_add:

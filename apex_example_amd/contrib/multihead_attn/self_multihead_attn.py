@@ -7,7 +7,8 @@ Parameter names follow Apex (``in_proj_weight`` / ``q_weight, k_weight,
 v_weight`` with ``separate_qkv_params``, ``out_proj_weight``,
 ``lyr_nrm_gamma_weights`` / ``lyr_nrm_beta_weights``) so state dicts carry over.
 ``impl='default'`` forces the PyTorch SDPA path; ``impl='fast'`` (default)
-uses the fused kernels whenever there is no mask.
+uses the fused kernels whenever there is no ``attn_mask``; with ``fused_attn_mask=True`` a
+boolean ``attn_mask`` [T, T] runs on them too.
 """
 from __future__ import annotations
 
@@ -24,7 +25,8 @@ from ._common import attention_bshd
 
 class SelfMultiheadAttn(nn.Module):
     def __init__(self, embed_dim, num_heads, dropout=0.0, bias=False, include_norm_add=False,
-                 impl="fast", separate_qkv_params=False, mask_additive=False):
+                 impl="fast", separate_qkv_params=False, mask_additive=False,
+                 fused_attn_mask=False):
         super().__init__()
         self.embed_dim = embed_dim
         self.num_heads = num_heads
@@ -34,6 +36,8 @@ class SelfMultiheadAttn(nn.Module):
         self.bias = bias
         self.include_norm_add = include_norm_add
         self.impl = impl
+        # a boolean attn_mask goes to the fused kernels (bit tiles) instead of SDPA
+        self.fused_attn_mask = fused_attn_mask
         self.scaling = self.head_dim ** -0.5
         self.separate_qkv_params = separate_qkv_params
         self.mask_additive = mask_additive
@@ -109,7 +113,8 @@ class SelfMultiheadAttn(nn.Module):
         q, k, v = qkv.permute(1, 0, 2, 3, 4).unbind(2)  # [B, T, H, D] strided views
         p = self.dropout if (is_training and self.training) else 0.0
         o = attention_bshd(q, k, v, p, key_padding_mask, attn_mask, self.mask_additive,
-                           allow_fused=(self.impl == "fast"))
+                           allow_fused=(self.impl == "fast"),
+                           fused_attn_mask=self.fused_attn_mask)
         o = o.transpose(0, 1).reshape(T, B, E)
         out = F.linear(o, self.out_proj_weight, self.out_proj_bias)
         if self.include_norm_add:

@@ -27,6 +27,19 @@ keys are all masked are skipped (no loads, no math) wherever they lie, masked ke
 get exactly zero dK / dV, and a query whose keys are all masked gets o = 0 and
 dq = 0 (its lse is unspecified) instead of NaN.
 
+Pair masks: ``attn_mask`` is a boolean [Sq, Sk] or [B, Sq, Sk] tensor, True = masked pair
+(Apex's time mask; sliding windows, block-diagonal document masks, prefix-LM, causal plus
+padding).  ``prepare_attn_mask`` packs it into bit tiles in one launch without a host sync
+(csrc/hip/attention_pairmask.hip): one 64-bit word per (query, 64-key tile) for the forward
+and dQ kernels, its transpose for dK/dV, and a class byte per tile, so that tiles with no
+attended pair are skipped wherever they lie, tiles where every pair attends run the
+mask-free math and only mixed tiles test bits.  A boolean ``key_padding_mask`` is OR-ed in
+by the prepare step; pass the returned ``PreparedAttnMask`` in place of the tensor to share
+it between layers.  Fully masked queries and keys behave as under a key mask.  It excludes
+``causal`` (put the triangle in the mask) and ``key_bias`` (an additive bias beside a pair
+mask stays on SDPA).  Timings against SDPA with the same mask and against the causal
+kernel: docs/PERF.md, "Attention: boolean pair masks".
+
 Packed variable-length sequences: ``fused_attention_varlen(q, k, v, cu_seqlens)`` takes
 [T, H, D] views holding only the real tokens of B sequences, sequence b owning rows
 ``cu_seqlens[b] .. cu_seqlens[b+1]-1`` (int32 [B + 1] on the GPU, read by the kernels), and
@@ -38,8 +51,8 @@ with key masks or unequal query / key lengths.
 
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size and head count (the query and key lengths may differ), no mask other than
-a per-batch key mask (a [Tq, Tk] ``attn_mask`` is not fused) or, at equal lengths, the
-causal mask; packed sequences ([T, H, D] with ``cu_seqlens``): q, k and v of one token
+a per-batch key mask, a boolean pair mask (an additive [Tq, Tk] ``attn_mask`` is not
+fused) or, at equal lengths, the causal mask; packed sequences ([T, H, D] with ``cu_seqlens``): q, k and v of one token
 and head count, self-attention per sequence, optional causal mask, no key mask.  Callers
 fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
@@ -151,6 +164,91 @@ def _key_mask(key_padding_mask, key_bias, like):
     return m.bias, m.live
 
 
+class PreparedAttnMask:
+    """A boolean pair mask as the bit tiles the kernels read (``prepare_attn_mask``), set
+    bit = attend, Bm = 1 (``B`` None: shared by the batch) or B:
+    ``wq`` uint64 [Bm, ceil(Sq/128), ceil(Sk/64), 128] (a query's 64 keys per word) with the
+    tile classes ``cq`` uint8 [Bm, ceil(Sq/128), ceil(Sk/64)] (0 dead, 1 mixed, 2 full), and
+    the transpose ``wk`` [Bm, ceil(Sk/128), ceil(Sq/64), 128], ``ck`` for dK/dV."""
+
+    __slots__ = ("wq", "cq", "wk", "ck", "B", "Sq", "Sk")
+
+    def __init__(self, wq, cq, wk, ck, B, Sq, Sk):
+        self.wq, self.cq, self.wk, self.ck, self.B, self.Sq, self.Sk = wq, cq, wk, ck, B, Sq, Sk
+
+
+def _bool_mask(m, what, dims, shape_text):
+    if not isinstance(m, torch.Tensor) or m.dim() not in dims:
+        raise ValueError("%s must be a %s tensor, got %s" % (
+            what, shape_text, tuple(m.shape) if isinstance(m, torch.Tensor) else type(m).__name__))
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s must be bool (True = masked), got %s" % (what, m.dtype))
+    if not m.is_cuda:
+        raise ValueError("%s must be on the GPU, got a %s tensor" % (what, m.device))
+    return m.detach().contiguous()
+
+
+def prepare_attn_mask(attn_mask: torch.Tensor, key_padding_mask=None) -> PreparedAttnMask:
+    """attn_mask: bool / uint8 [Sq, Sk] or [B, Sq, Sk] on the GPU, True / non-zero = masked
+    pair; key_padding_mask: optional bool [B, Sk], True = masked key, OR-ed in (the result
+    is then per batch element).  One kernel launch, no host sync (graph-capture safe); the
+    result serves every fused attention call of the same (B, Sq, Sk), forward and backward."""
+    m = _bool_mask(attn_mask, "attn_mask", (2, 3), "[Sq, Sk] or [B, Sq, Sk]")
+    Sq, Sk = m.shape[-2:]
+    B = m.size(0) if m.dim() == 3 else None
+    kp = None
+    if key_padding_mask is not None:
+        kp = _bool_mask(key_padding_mask, "key_padding_mask", (2,), "[B, Sk]")
+        if kp.size(1) != Sk or (B is not None and kp.size(0) != B) or kp.device != m.device:
+            raise ValueError("key_padding_mask %s on %s does not fit attn_mask %s on %s" % (
+                tuple(kp.shape), kp.device, tuple(m.shape), m.device))
+        B = kp.size(0)
+    if Sq == 0 or Sk == 0:
+        raise ValueError("attn_mask must have queries and keys, got %s" % (tuple(m.shape),))
+    words, cls = _C().prepare_attn_mask(m, kp)
+    Bm = 1 if B is None else B
+    nq = (-(-Sq // 128), -(-Sk // 64))
+    nk = (-(-Sk // 128), -(-Sq // 64))
+    nwq, ncq = Bm * nq[0] * nq[1] * 128, Bm * nq[0] * nq[1]
+    words = words.view(torch.uint64)
+    return PreparedAttnMask(words[:nwq].view(Bm, *nq, 128), cls[:ncq].view(Bm, *nq),
+                            words[nwq:].view(Bm, *nk, 128), cls[ncq:].view(Bm, *nk), B, Sq, Sk)
+
+
+def _attn_mask(attn_mask, causal, key_padding_mask, key_bias, q, like):
+    """The ``PreparedAttnMask`` of a call with ``attn_mask`` for the queries ``q``
+    [B, Sq, ...] and the keys ``like`` [B, Sk, ...]."""
+    if causal:
+        raise ValueError("attn_mask excludes causal=True: put the triangle in the mask")
+    if key_bias is not None:
+        raise ValueError("attn_mask excludes key_bias: an additive bias beside a pair mask is "
+                         "not fused")
+    B, Sq, Sk = q.size(0), q.size(1), like.size(1)
+    m = attn_mask
+    if isinstance(m, PreparedAttnMask):
+        if key_padding_mask is not None:
+            raise ValueError("a PreparedAttnMask already holds its key_padding_mask")
+    else:
+        if not isinstance(m, torch.Tensor) or m.dim() not in (2, 3) or \
+                tuple(m.shape[-2:]) != (Sq, Sk) or (m.dim() == 3 and m.size(0) != B):
+            raise ValueError("attn_mask must be [Sq, Sk] = [%d, %d] or [B, Sq, Sk] with B = %d, "
+                             "got %s" % (Sq, Sk, B, tuple(m.shape) if isinstance(m, torch.Tensor)
+                                         else type(m).__name__))
+        if isinstance(key_padding_mask, PreparedKeyMask):
+            raise ValueError("attn_mask takes the boolean key_padding_mask tensor, not a "
+                             "PreparedKeyMask")
+        if key_padding_mask is not None and tuple(key_padding_mask.shape) != (B, Sk):
+            raise ValueError("key mask must be [B, S] = [%d, %d], got %s" % (
+                B, Sk, tuple(key_padding_mask.shape)))
+        m = prepare_attn_mask(m, key_padding_mask)
+    if (m.Sq, m.Sk) != (Sq, Sk) or m.B not in (None, B):
+        raise ValueError("prepared attn_mask is for [B, Sq, Sk] = [%s, %d, %d], the call's is "
+                         "[%d, %d, %d]" % (m.B, m.Sq, m.Sk, B, Sq, Sk))
+    if m.wq.device != q.device:
+        raise ValueError("attn_mask is on %s, q on %s" % (m.wq.device, q.device))
+    return m
+
+
 def _check_causal(causal, Sq, Sk):
     if causal and Sq != Sk:
         raise ValueError("causal attention needs equal query and key lengths, got Sq = %d, "
@@ -176,7 +274,8 @@ class AttentionFunction(torch.autograd.Function):
     None or, with the "varlen_*" layouts ([T, H, D] views of packed sequences, o
     [T, H, D]), the pair (cu_seqlens int32 [B + 1], max_seqlen); it rides in ``ctx``
     outside autograd's saved tensors, so a captured graph may be replayed on new offsets
-    written into the same tensor.  The backward
+    written into the same tensor.  The same slot takes a ``PreparedAttnMask`` instead (a
+    pair mask: no causal flag, no key mask; it takes no gradient).  The backward
     returns one gradient per input: packed inputs (and the q beside a packed kv: a
     time-first projection gets its gradient back as a view, no transpose copy) get theirs
     in their own layout, separate q, k, v dense ones."""
@@ -188,6 +287,9 @@ class AttentionFunction(torch.autograd.Function):
         ctx.varlen = varlen
         if varlen is None:
             o, lse = _C().fwd(q, k, v, *ctx.cfg[1:], kbias, klive)
+        elif isinstance(varlen, PreparedAttnMask):
+            m = varlen
+            o, lse = _C().fwd_amask(q, k, v, *ctx.cfg[2:], m.wq, m.cq, m.wk, m.ck)
         else:
             o, lse = _C().fwd_varlen(q, k, v, *varlen, *ctx.cfg[1:])
         ctx.save_for_backward(*inputs, o, lse, kbias, klive)
@@ -204,6 +306,10 @@ class AttentionFunction(torch.autograd.Function):
         if ctx.varlen is None:
             _C().bwd(do, *_SPLIT[layout](inputs), o, lse, *cfg, *_SPLIT[layout](grads), kbias,
                      klive)
+        elif isinstance(ctx.varlen, PreparedAttnMask):
+            m = ctx.varlen
+            _C().bwd_amask(do, *_SPLIT[layout](inputs), o, lse, *cfg[1:],
+                           *_SPLIT[layout](grads), m.wq, m.cq, m.wk, m.ck)
         else:
             _C().bwd_varlen(do, *_SPLIT[layout](inputs), o, lse, *ctx.varlen, *cfg,
                             *_SPLIT[layout](grads))
@@ -233,35 +339,50 @@ class FusedKVAttentionFunction:
 
 
 def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
-                    key_bias=None):
+                    key_bias=None, attn_mask=None):
     """q: [B, Sq, H, D], k, v: [B, Sk, H, D] -> o [B, Sq, H, D] (Sq != Sk is
     cross-attention; ``causal`` needs Sq == Sk).  key_padding_mask: [B, Sk] bool, True =
     masked key; key_bias: [B, Sk] float, added to the scaled scores; either may be a
-    ``PreparedKeyMask``."""
+    ``PreparedKeyMask``.  attn_mask: bool [Sq, Sk] / [B, Sq, Sk], True = masked pair, or a
+    ``PreparedAttnMask``; it excludes ``causal`` and ``key_bias`` and merges a boolean
+    ``key_padding_mask``."""
     _check_causal(causal, q.size(1), k.size(1))
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
+    if attn_mask is not None:
+        m = _attn_mask(attn_mask, causal, key_padding_mask, key_bias, q, k)
+        return AttentionFunction.apply("qkv", False, dropout_p, scale, _seed(dropout_p), None,
+                                       None, m, q, k, v)
     kbias, klive = _key_mask(key_padding_mask, key_bias, k)
     return FusedAttentionFunction.apply(q, k, v, causal, dropout_p, scale, _seed(dropout_p),
                                         kbias, klive)
 
 
-def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, key_bias=None):
+def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, key_bias=None,
+                       attn_mask=None):
     """q: [B, Sq, H, D], kv: [B, Sk, 2, H, D] (the packed output of a fused KV
     projection, any strides) -> o [B, Sq, H, D]; the backward writes dK and dV into one
-    packed dkv of kv's layout.  Masks are [B, Sk], as in ``fused_attention``."""
+    packed dkv of kv's layout.  Masks as in ``fused_attention``."""
     if kv.dim() != 5 or kv.size(2) != 2:
         raise ValueError("kv must be [B, Sk, 2, H, D], got %s" % (tuple(kv.shape),))
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
+    if attn_mask is not None:
+        m = _attn_mask(attn_mask, False, key_padding_mask, key_bias, q, kv)
+        return AttentionFunction.apply("q_packed_kv", False, dropout_p, scale, _seed(dropout_p),
+                                       None, None, m, q, kv)
     kbias, klive = _key_mask(key_padding_mask, key_bias, kv)
     return FusedKVAttentionFunction.apply(q, kv, dropout_p, scale, _seed(dropout_p),
                                           kbias, klive)
 
 
 def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
-                        key_bias=None):
+                        key_bias=None, attn_mask=None):
     """qkv: [B, S, 3, H, D] (any strides) -> o [B, S, H, D]; the backward returns one
     packed dqkv of qkv's layout.  Masks as in ``fused_attention``."""
     scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
+    if attn_mask is not None:
+        m = _attn_mask(attn_mask, causal, key_padding_mask, key_bias, qkv, qkv)
+        return AttentionFunction.apply("packed_qkv", False, dropout_p, scale, _seed(dropout_p),
+                                       None, None, m, qkv)
     kbias, klive = _key_mask(key_padding_mask, key_bias, qkv)
     return FusedQKVAttentionFunction.apply(qkv, causal, dropout_p, scale, _seed(dropout_p),
                                            kbias, klive)

@@ -57,6 +57,16 @@
 // keep their sequence-local indices, lse / D their [B, H, Sp] rows with Sp from the
 // launch's max_seqlen, which also sizes the grid.  The VARLEN = false instantiations are
 // the kernels unchanged.
+//
+// Pair masks (AMASK kernels, CAUSAL = KMASK = VARLEN = false): a boolean [Sq, Sk] mask as
+// the bit tiles of attention_pairmask.hip (read its header), which also compiles these
+// instantiations.  A lane's mask of a tile is one 64-bit word; the words of a workgroup's
+// 128 rows ride the ring beside the tile (1 KiB more per slot); the kernels walk the
+// non-dead tiles of their row of tile classes (PairTiles), run full tiles through the
+// mask-free math and, on mixed tiles, test each accumulator register's compile-time bit.
+// Fully masked queries and keys follow KMASK (o = 0, lse = -inf, dq = 0, dk = dv = 0; the
+// dQ kernel leaves the guarded lse and the refined D behind D).  The AMASK = false
+// instantiations are the kernels unchanged.
 #include "attention_common.h"
 
 namespace amd {
@@ -87,7 +97,7 @@ __global__ void __launch_bounds__(64) attn_kmask_prep_k(const M* __restrict__ ma
 }
 
 // ---------------------------------------------------------------------------- forward
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
@@ -95,7 +105,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int KV = 2 * kAKT * kARow;          // K and V images of one tile
-  constexpr int BUF = KV + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
+  // KMASK: + the tile's 64 bias floats; AMASK: + the tile's 128 mask words
+  constexpr int BUF = KV + (KMASK || AMASK ? 1024 : 0);
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];  // 2 x (K, V[, bias])
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform to the compiler
@@ -142,11 +153,16 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
     vof[i] = row_off<T>(row, a.vss, (swz_tr(row, pch) - row * kARow) >> 4);
   }
   const float* kbias = KMASK ? a.kbias + (int64_t)b * kstride : nullptr;
+  // AMASK: row `tile` of this batch element's mask words, 1 KiB per key tile
+  const unsigned long long* wrow = AMASK ? a.wq + (b * a.mqs + (int64_t)tile * nkt) * 128 : nullptr;
   auto issue = [&](int kt, int buf) {
     unsigned char* Kl = lds + buf * BUF;
     unsigned char* Vl = Kl + kAKT * kARow;
     if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
       if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, Kl + KV);
+    }
+    if constexpr (AMASK) {  // two words per lane: the tile's 128 queries
+      if (wid == 0) glds16(wrow + kt * 128 + lane * 2, Kl + KV);
     }
     if ((kt + 1) * kAKT <= Sk) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
@@ -194,10 +210,11 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
         vhi[dt][t][s] = tr_addr(r0 + 8, c0, lane);
       }
 
+  [[maybe_unused]] bool full = false;  // AMASK: every pair of the tile in hand attends
   auto step = [&](int kt, int buf, int nx) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (KMASK) {
+    if constexpr (KMASK || AMASK) {
       if (nx < nkt) issue(nx, buf ^ 1);
     } else {
       if (kt + 1 < nkt) issue(kt + 1, buf ^ 1);
@@ -261,11 +278,38 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
           psum += p;
           x[t][r] = p;
         }
+    } else if (AMASK && !full) {
+      // mixed tile (wave-uniform): -inf where the lane's bit of the pair is clear (bits past
+      // Sq / Sk are clear), then the key-mask path's -inf-safe running max
+      const uint2 w = pair_word(Kl + KV, wid * 32 + c32, hl);
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          x[t][r] = pair_bit(w, t, r) ? x[t][r] * a.scale_log2 : -INFINITY;
+          tmax = fmaxf(tmax, x[t][r]);
+        }
+      tmax = max_halves(tmax);
+      const float mnew = fmaxf(m, tmax);
+      const float msafe = mnew == -INFINITY ? 0.f : mnew;
+      grow = __any(mnew != m);
+      alpha = grow ? fexp2(m - msafe) : 1.f;
+      m = mnew;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = fexp2(x[t][r] - msafe);
+          psum += p;
+          x[t][r] = p;
+        }
     } else {
       // mask (boundary / diagonal tiles only: the test is wave-uniform), running
-      // max on the raw scores, then one fma + exp2 per score in log2 units
+      // max on the raw scores, then one fma + exp2 per score in log2 units; an AMASK
+      // tile that gets here is full, which puts it inside Sq x Sk
       const bool need_mask =
-          (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+          !AMASK && ((k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32));
       if (need_mask) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -338,6 +382,16 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
       step(kt, slot, nx);
       kt = nx;
     }
+  } else if constexpr (AMASK) {
+    PairTiles pt(a.cq + b * a.mqs + (int64_t)tile * nkt, nkt, lane);
+    int kt = pt.next();
+    if (kt < nkt) issue(kt, 0);
+    for (int slot = 0; kt < nkt; slot ^= 1) {
+      full = pt.full;
+      const int nx = pt.next();
+      step(kt, slot, nx);
+      kt = nx;
+    }
   } else {
     issue(0, 0);
     for (int kt = 0; kt < nkt; ++kt) step(kt, kt & 1, 0);
@@ -365,7 +419,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
 // make the compiler's vmcnt waits drain the prefetch).  KMASK: a lane's key bias is
 // loop-invariant (one load); a workgroup whose 128 keys are all dead writes zeros and
 // leaves, a wave whose 32 keys are all dead keeps the ring's barriers and skips the math.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
@@ -373,7 +427,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;     // 8 KiB
-  constexpr int BUF = 4 * IMG + 1024;   // Q rows, Q tr, dO rows, dO tr, {lse, D}
+  // Q rows, Q tr, dO rows, dO tr, {lse, D}[, AMASK: the tile's 128 mask words]
+  constexpr int BUF = 4 * IMG + 1024 + (AMASK ? 1024 : 0);
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform to the compiler
@@ -417,8 +472,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
                               : 0u;
   const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
   const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + hh * a.dsh;
-  // KMASK: the guarded copy of lse that the dQ kernel left behind D
-  const float* lse = (KMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
+  // KMASK / AMASK: the guarded copy of lse that the dQ kernel left behind D
+  const float* lse = (KMASK || AMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
                      (int64_t)bh * a.lse_stride;
   const float* Dr = a.D + (int64_t)bh * a.lse_stride;
 
@@ -439,8 +494,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   const int nqt = (Sq + kAKT - 1) / kAKT;
   const int qt0 = CAUSAL ? kb0 / kAKT : 0;
   const int lrow = lane >> 3, pch = lane & 7;
+  // AMASK: row `tile` of this batch element's transposed mask words, 1 KiB per query tile
+  const unsigned long long* wrow = AMASK ? a.wk + (b * a.mks + (int64_t)tile * nqt) * 128 : nullptr;
   auto issue = [&](int qt, int buf) {
     unsigned char* base = lds + buf * BUF;
+    if constexpr (AMASK) {  // two words per lane: the tile's 128 keys
+      if (wid == 1) glds16(wrow + qt * 128 + lane * 2, base + 4 * IMG + 1024);
+    }
     if (wid == 0) {  // lanes 0-15: lse[q0 .. q0+63], 16-31: D[...], 32-63: pad (lse again)
       const int seg = (lane >> 4) & 1, part = lane & 15;
       const float* src = (seg ? Dr : lse) + qt * kAKT + part * 4;
@@ -487,12 +547,31 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
         thi[dt][h][s] = tr_addr(r0 + 8, c0, lane);
       }
 
-  if (qt0 < nqt) issue(qt0, 0);
-  for (int qt = qt0; qt < nqt; ++qt) {
+  // AMASK: qt walks the non-dead query tiles of this key tile's row of classes (nx = the
+  // one after qt, `full` the class of qt), the ring slot alternates
+  PairTiles pt(AMASK ? a.ck + b * a.mks + (int64_t)tile * nqt : nullptr, nqt, lane);
+  [[maybe_unused]] int nx = 0, slot = 0;
+  [[maybe_unused]] bool full = false;
+  if constexpr (AMASK) {
+    nx = pt.next();
+    if (nx < nqt) issue(nx, 0);
+  } else {
+    if (qt0 < nqt) issue(qt0, 0);
+  }
+  for (int qt = AMASK ? nx : qt0; qt < nqt; qt = AMASK ? nx : qt + 1) {
+    if constexpr (AMASK) {
+      full = pt.full;
+      nx = pt.next();
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (qt + 1 < nqt) issue(qt + 1, (qt + 1 - qt0) & 1);
-    const unsigned char* base = lds + ((qt - qt0) & 1) * BUF;
+    if constexpr (AMASK) {
+      if (nx < nqt) issue(nx, slot ^ 1);
+    } else {
+      if (qt + 1 < nqt) issue(qt + 1, (qt + 1 - qt0) & 1);
+    }
+    const unsigned char* base = lds + (AMASK ? slot : ((qt - qt0) & 1)) * BUF;
+    if constexpr (AMASK) slot ^= 1;
     const unsigned char* Qr = base;
     const unsigned char* Qt = base + IMG;
     const unsigned char* Or = base + 2 * IMG;
@@ -550,6 +629,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
       }
     };
     auto mask = [&](int h, f32x16_t& sc, f32x16_t& dp) {
+      if constexpr (AMASK) {  // this lane's key against the half's 32 queries (0 past Sq)
+        const uint2 w = pair_word(base + 4 * IMG + 1024, wid * 32 + c32, hl);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!pair_bit(w, h, r)) sc[r] = dp[r] = 0.f;
+        return;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int q = q0 + 32 * h + 8 * (r >> 2) + 4 * hl + (r & 3);
@@ -575,7 +661,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     // KMASK takes the half-by-half path always: the straight-line block sits at 246-256
     // VGPRs, and the bias on top of that spilled (1-33 VGPRs, reloaded inside the loop)
     // in whichever instantiation the register allocator liked least.
-    const bool clean = (q0 + kAKT <= Sq) && (!CAUSAL || kw0 + 31 <= q0);
+    // AMASK: a full tile is clean, a mixed one masks both halves by its bits.
+    const bool clean = AMASK ? full : (q0 + kAKT <= Sq) && (!CAUSAL || kw0 + 31 <= q0);
     if (!KMASK && clean) {
       f32x16_t sc0, dp0, sc1, dp1;
       sdp(0, sc0, dp0);
@@ -593,7 +680,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
         sdp(h, sc, dp);
         softmax_bwd(h, sc, dp);
         // wave-uniform: does any (query, key) of this 32 x 32 block need a mask?
-        if ((qh0 + 31 >= Sq) || (CAUSAL && kw0 + 31 > qh0)) mask(h, sc, dp);
+        if (AMASK || (qh0 + 31 >= Sq) || (CAUSAL && kw0 + 31 > qh0)) mask(h, sc, dp);
         accum(h, sc, dp);
       }
     }
@@ -615,7 +702,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
 // K sits in LDS as a row image (A of S^T) and a transposed image (A of dQ^T);
 // V as a row image (A of dP^T = V . dO^T).  KMASK: the tile's bias rides the ring and
 // dead tiles are skipped as in the forward.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
@@ -623,7 +710,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int IMG = kAKT * kARow;
-  constexpr int BUF = 3 * IMG + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
+  // KMASK: + the tile's 64 bias floats; AMASK: + the tile's 128 mask words
+  constexpr int BUF = 3 * IMG + (KMASK || AMASK ? 1024 : 0);
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform to the compiler
@@ -657,7 +745,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       of[s] = *reinterpret_cast<const v8*>(Op + 16 * s + 8 * hl);
     }
   }
-  const float lse_q = KMASK ? lse_guard(a.lse[(int64_t)bh * a.lse_stride + qq])
+  const float lse_q = KMASK || AMASK ? lse_guard(a.lse[(int64_t)bh * a.lse_stride + qq])
                             : a.lse[(int64_t)bh * a.lse_stride + qq];
   // D = rowsum(dO * O) of this lane's query, from the dO fragments already in
   // registers (the two 32-lane halves hold complementary d ranges); written for the
@@ -674,7 +762,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       for (int j = 0; j < 8; ++j) part = fmaf((float)of[s][j], (float)ov[j], part);
     }
     D_q = part + __shfl_xor(part, 32);
-    if constexpr (KMASK) {  // D itself: refined at the end; here the guarded lse, so the
+    if constexpr (KMASK || AMASK) {  // D itself: refined at the end; here the guarded lse, so the
                             // dK/dV kernel need not guard per score
       if (hl == 0 && q < Sq) a.D[((int64_t)a.B * a.H + bh) * a.lse_stride + q] = lse_q;
     } else {
@@ -699,10 +787,15 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   }
   // images per buffer: 0 = K rows, 1 = K transposed, 2 = V rows[, 3 = bias]
   const float* kbias = KMASK ? a.kbias + (int64_t)b * kstride : nullptr;
+  // AMASK: row `tile` of this batch element's mask words, 1 KiB per key tile
+  const unsigned long long* wrow = AMASK ? a.wq + (b * a.mqs + (int64_t)tile * nkt) * 128 : nullptr;
   auto issue = [&](int kt, int buf) {
     unsigned char* base = lds + buf * BUF;
     if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
       if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, base + 3 * IMG);
+    }
+    if constexpr (AMASK) {  // two words per lane: the tile's 128 queries
+      if (wid == 0) glds16(wrow + kt * 128 + lane * 2, base + 3 * IMG);
     }
     if ((kt + 1) * kAKT <= Sk) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
@@ -759,26 +852,35 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
         thi[dt][t][s] = tr_addr(r0 + 8, c0, lane);
       }
 
-  // KMASK: kt walks the live tiles only (nx = the one after kt), the ring slot alternates
+  // KMASK: kt walks the live tiles only (nx = the one after kt), the ring slot alternates;
+  // AMASK: the same over the non-dead tiles of the classes, `full` the class of kt
+  constexpr bool WALK = KMASK || AMASK;
   LiveTiles lt(KMASK ? a.klive + (int64_t)b * (kstride / kAKT) : nullptr, nkt, lane);
+  PairTiles pt(AMASK ? a.cq + b * a.mqs + (int64_t)tile * nkt : nullptr, nkt, lane);
+  [[maybe_unused]] bool full = false;
+  auto next_tile = [&]() {
+    if constexpr (AMASK) return pt.next();
+    else return lt.next();
+  };
   int nx = 0, slot = 0;
-  if constexpr (KMASK) {
-    nx = lt.next();
+  if constexpr (WALK) {
+    nx = next_tile();
     if (nx < nkt) issue(nx, 0);
   } else {
     issue(0, 0);
   }
-  for (int kt = KMASK ? nx : 0; kt < nkt; kt = KMASK ? nx : kt + 1) {
-    if constexpr (KMASK) nx = lt.next();
+  for (int kt = WALK ? nx : 0; kt < nkt; kt = WALK ? nx : kt + 1) {
+    if constexpr (AMASK) full = pt.full;
+    if constexpr (WALK) nx = next_tile();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (KMASK) {
+    if constexpr (WALK) {
       if (nx < nkt) issue(nx, slot ^ 1);
     } else {
       if (kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);
     }
-    const unsigned char* base = lds + (KMASK ? slot : (kt & 1)) * BUF;
-    if constexpr (KMASK) slot ^= 1;
+    const unsigned char* base = lds + (WALK ? slot : (kt & 1)) * BUF;
+    if constexpr (WALK) slot ^= 1;
     const unsigned char* Kr = base;
     const unsigned char* Kt = base + IMG;
     const unsigned char* Vr = base + 2 * IMG;
@@ -818,6 +920,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       }
     };
     auto mask = [&](int t, f32x16_t& sc) {
+      if constexpr (AMASK) {  // this lane's query against the half's 32 keys (0 past Sk)
+        const uint2 w = pair_word(base + 3 * IMG, wid * 32 + c32, hl);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!pair_bit(w, t, r)) sc[r] = 0.f;
+        return;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
@@ -825,7 +934,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       }
     };
     auto accum = [&](int t, const f32x16_t& sc) {
-      if constexpr (KMASK) {
+      if constexpr (KMASK || AMASK) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dsum += sc[r];
       }
@@ -842,7 +951,9 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
     sdp(1, sc1, dp1);
     // wave-uniform; unmasked tiles run as one straight-line block (half 0's dQ MFMAs
     // beside half 1's softmax VALU)
-    const bool need_mask = (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+    // (AMASK: a full tile needs none, a mixed one is masked by its bits)
+    const bool need_mask =
+        AMASK ? !full : (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
     if (!need_mask) {
       dsoft(0, sc0, dp0);
       accum(0, sc0);
@@ -857,7 +968,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
       accum(1, sc1);
     }
   }
-  if constexpr (KMASK) {
+  if constexpr (KMASK || AMASK) {
     const float dD = dsum + __shfl_xor(dsum, 32);  // the two halves hold 32 keys each per tile
     if (hl == 0 && q < Sq) a.D[(int64_t)bh * a.lse_stride + q] = D_q + dD;
   }
@@ -869,6 +980,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
 
 }  // namespace
 
+#ifndef ATTN_PAIRMASK_TU  // attention_pairmask.hip includes this file for the kernels alone
 int attn_lse_stride(int S) { return (S + kAKT - 1) / kAKT * kAKT; }
 
 void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, float* bias,
@@ -898,6 +1010,7 @@ static bool head_dim_128(const char* who, int D) {
 
 void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
   if (head_dim_128("attn_fwd", p.D)) return attn_fwd_d128(p, o, lse, st);
+  if (p.wq != nullptr) return attn_fwd_amask64(p, o, lse, st);
   AttnArgs a = kernel_args<AttnArgs>("attn_fwd", p);
   a.o = o; a.lse = lse;
   dim3 grid((p.Sq + 127) / 128, p.B * p.H), block(kAT);
@@ -908,6 +1021,7 @@ void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
 
 void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
   if (head_dim_128("attn_bwd", p.D)) return attn_bwd_d128(p, g, st);
+  if (p.wq != nullptr) return attn_bwd_amask64(p, g, st);
   AttnBwdArgs a = bwd_kernel_args("attn_bwd", p, g);
   // dQ owns 128-query tiles, dK/dV 128-key tiles; dQ first (it writes D), then dK/dV
   dim3 qgrid((p.Sq + 127) / 128, p.B * p.H), kgrid((p.Sk + 127) / 128, p.B * p.H), block(kAT);
@@ -917,5 +1031,7 @@ void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
   });
 }
 #undef ATTN_KERNEL
+#undef ATTN_AMASK_KERNEL
+#endif  // ATTN_PAIRMASK_TU
 
 }  // namespace amd

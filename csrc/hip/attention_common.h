@@ -212,6 +212,12 @@ struct AttnArgs {
   const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
   const int* cu;               // VARLEN: [B + 1] first token row of each sequence
   int T;                       // VARLEN: rows of the packed views
+  // AMASK: the prepared pair mask (amd_kernels.h), batch strides in tiles (0 = shared)
+  const unsigned long long* wq;
+  const unsigned char* cq;
+  const unsigned long long* wk;
+  const unsigned char* ck;
+  int64_t mqs, mks;
 };
 
 // The live key tiles of one batch element, in order: ballots 64 liveness bytes at a time
@@ -237,6 +243,43 @@ struct LiveTiles {
     return kt;
   }
 };
+
+// AMASK: the non-dead tiles of one row of tile classes (cq: the key tiles of a 128-query
+// tile; ck: the query tiles of a 128-key tile), in order, as LiveTiles walks liveness bytes;
+// the same load and a second ballot tell whether the tile is full (class 2: every pair
+// attends, the mask-free math serves) or mixed (class 1: the lane tests its bits).
+struct PairTiles {
+  const unsigned char* cls;
+  int n, lane, c0;
+  unsigned long long lm, fm;
+  bool full;  // the class of the tile next() returned last
+  __device__ __forceinline__ PairTiles(const unsigned char* cls_, int n_, int lane_)
+      : cls(cls_), n(n_), lane(lane_), c0(-64), lm(0), fm(0), full(false) {}
+  __device__ __forceinline__ int next() {
+    while (lm == 0) {
+      c0 += 64;
+      if (c0 >= n) return n;
+      const int t = c0 + lane;
+      const int c = t < n ? cls[t] : 0;
+      lm = __ballot(c != 0);
+      fm = __ballot(c == 2);
+    }
+    const int i = __builtin_ctzll(lm);
+    full = (fm >> i) & 1;
+    lm &= lm - 1;
+    return c0 + i;
+  }
+};
+// a lane's 64-bit mask word of a tile (its query's 64 keys, or its key's 64 queries) as the
+// two 32-bit halves shifted down by 4 hl: bit (r & 3) + 8 (r >> 2) of half t is then the
+// pair of accumulator register r of 32-row half t, a compile-time position
+__device__ __forceinline__ uint2 pair_word(const unsigned char* blk, int row, int hl) {
+  const uint2 w = *reinterpret_cast<const uint2*>(blk + 8 * row);
+  return uint2{w.x >> (4 * hl), w.y >> (4 * hl)};
+}
+__device__ __forceinline__ bool pair_bit(const uint2& w, int t, int r) {
+  return (((t ? w.y : w.x) >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0;
+}
 
 // VARLEN: sequence b of a packed batch, rows cu[b] .. cu[b + 1] - 1 of [T, H, D] views -
 // two scalar loads, wave-uniform.  The length is clipped to the launch's max_seqlen (the
@@ -308,6 +351,12 @@ struct AttnBwdArgs {
   const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
   const int* cu;               // VARLEN: [B + 1] first token row of each sequence
   int T;                       // VARLEN: rows of the packed views
+  // AMASK: the prepared pair mask (amd_kernels.h), batch strides in tiles (0 = shared)
+  const unsigned long long* wq;
+  const unsigned char* cq;
+  const unsigned long long* wk;
+  const unsigned char* ck;
+  int64_t mqs, mks;
 };
 
 // A query none of whose keys is live has lse = -inf (or whatever the caller stored);
@@ -336,6 +385,15 @@ static void require_no_mask_when_packed(const char* who, const AttnProblem& p) {
     abort();
   }
 }
+static void require_pair_mask_alone(const char* who, const AttnProblem& p) {
+  if (p.wq == nullptr) return;
+  if (p.causal || p.kbias != nullptr || p.cu_seqlens != nullptr || p.cq == nullptr ||
+      p.wk == nullptr || p.ck == nullptr) {
+    fprintf(stderr, "%s: a pair mask comes whole (wq, cq, wk, ck) and takes no causal flag, key "
+                    "mask or cu_seqlens: its bits hold those shapes\n", who);
+    abort();
+  }
+}
 static void require_causal_square(const char* who, bool causal, int Sq, int Sk) {
   if (causal && Sq != Sk) {
     fprintf(stderr, "%s: causal needs equal query and key lengths, got Sq = %d, Sk = %d\n", who,
@@ -353,6 +411,7 @@ template <typename A>
 A kernel_args(const char* who, const AttnProblem& p) {
   require_causal_square(who, p.causal, p.Sq, p.Sk);
   require_no_mask_when_packed(who, p);
+  require_pair_mask_alone(who, p);
   A a{};
   a.q = p.q.p; a.qsb = p.q.sb; a.qss = p.q.ss; a.qsh = p.q.sh;
   a.k = p.k.p; a.ksb = p.k.sb; a.kss = p.k.ss; a.ksh = p.k.sh;
@@ -366,6 +425,9 @@ A kernel_args(const char* who, const AttnProblem& p) {
   a.seed = p.seed;
   a.kbias = p.kbias; a.klive = p.klive;
   a.cu = p.cu_seqlens; a.T = p.T;
+  a.wq = p.wq; a.cq = p.cq; a.wk = p.wk; a.ck = p.ck;
+  a.mqs = p.pm_sb;
+  a.mks = p.pm_sb ? (int64_t)((p.Sk + 127) / 128) * ((p.Sq + kAKT - 1) / kAKT) : 0;
   return a;
 }
 
@@ -405,12 +467,25 @@ void dispatch(const AttnProblem& p, bool drop, F f) {
 // the kernel `name` instantiated for dispatch's (t, c, d, m, vl)
 #define ATTN_KERNEL(name)                                                                    \
   name<typename decltype(t)::type, decltype(c)::value, decltype(d)::value, decltype(m)::value, \
-       decltype(vl)::value>
+       decltype(vl)::value, false>
+
+// f(Elem<T>, drop): the 2 x 2 pair-mask (AMASK) instantiations, which exclude the other three
+template <typename F>
+void dispatch_amask(const AttnProblem& p, bool drop, F f) {
+  auto flags = [&](auto t) { drop ? f(t, std::true_type{}) : f(t, std::false_type{}); };
+  if (p.dtype == DType::BF16) flags(Elem<bf16_t>{});
+  else flags(Elem<half_t>{});
+}
+#define ATTN_AMASK_KERNEL(name) \
+  name<typename decltype(t)::type, false, decltype(d)::value, false, false, true>
 
 }  // namespace
 
 // the head dim 128 kernels (attention_d128.hip), reached through attn_fwd / attn_bwd
 void attn_fwd_d128(const AttnProblem& p, void* o, float* lse, hipStream_t st);
 void attn_bwd_d128(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
+// the head dim 64 kernels under a pair mask (attention_pairmask.hip compiles them)
+void attn_fwd_amask64(const AttnProblem& p, void* o, float* lse, hipStream_t st);
+void attn_bwd_amask64(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 
 }  // namespace amd

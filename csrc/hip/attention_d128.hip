@@ -117,13 +117,14 @@ __device__ __forceinline__ void settle(V (&f)[N]) {
 }
 
 // ---------------------------------------------------------------------------- forward
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
 __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
   int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
   constexpr int KV = 2 * kTile;                 // K and V tile images: 32 KiB
-  constexpr int BUF = KV + (KMASK ? 1024 : 0);  // KMASK: + the tile's 64 bias floats
+  // KMASK: + the tile's 64 bias floats; AMASK: + the tile's 128 mask words
+  constexpr int BUF = KV + (KMASK || AMASK ? 1024 : 0);
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -169,11 +170,16 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
     vof[i] = row_off<T>(row, a.vss, (swz_tr(row, pch) - row * kARow) >> 4);
   }
   const float* kbias = KMASK ? a.kbias + (int64_t)b * kstride : nullptr;
+  // AMASK: row `tile` of this batch element's mask words, 1 KiB per key tile
+  const unsigned long long* wrow = AMASK ? a.wq + (b * a.mqs + (int64_t)tile * nkt) * 128 : nullptr;
   auto issue = [&](int kt, int buf) {
     unsigned char* Kl = lds + buf * BUF;
     unsigned char* Vl = Kl + kTile;
     if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
       if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, Kl + KV);
+    }
+    if constexpr (AMASK) {  // two words per lane: the tile's 128 queries
+      if (wid == 0) glds16(wrow + kt * 128 + lane * 2, Kl + KV);
     }
     if ((kt + 1) * kAKT <= Sk) {
       dma_tile<T>(tile_base(K, kt * kAKT, a.kss), kof, Kl, wid);
@@ -216,10 +222,11 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
         vhi[dt][t][s] = tr_addr(r0 + 8, c0, lane);
       }
 
+  [[maybe_unused]] bool full = false;  // AMASK: every pair of the tile in hand attends
   auto step = [&](int kt, int buf, int nx) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (KMASK) {
+    if constexpr (KMASK || AMASK) {
       if (nx < nkt) issue(nx, buf ^ 1);
     } else {
       if (kt + 1 < nkt) issue(kt + 1, buf ^ 1);
@@ -281,11 +288,38 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
           psum += p;
           x[t][r] = p;
         }
+    } else if (AMASK && !full) {
+      // mixed tile (wave-uniform): -inf where the lane's bit of the pair is clear (bits past
+      // Sq / Sk are clear), then the key-mask path's -inf-safe running max
+      const uint2 w = pair_word(Kl + KV, wid * 32 + c32, hl);
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          x[t][r] = pair_bit(w, t, r) ? x[t][r] * a.scale_log2 : -INFINITY;
+          tmax = fmaxf(tmax, x[t][r]);
+        }
+      tmax = max_halves(tmax);
+      const float mnew = fmaxf(m, tmax);
+      const float msafe = mnew == -INFINITY ? 0.f : mnew;
+      grow = __any(mnew != m);
+      alpha = grow ? fexp2(m - msafe) : 1.f;
+      m = mnew;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = fexp2(x[t][r] - msafe);
+          psum += p;
+          x[t][r] = p;
+        }
     } else {
       // mask (boundary / diagonal tiles only: wave-uniform test), running max on the raw
-      // scores, then one fma + exp2 per score in log2 units
+      // scores, then one fma + exp2 per score in log2 units; an AMASK tile that gets here is
+      // full, which puts it inside Sq x Sk
       const bool need_mask =
-          (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+          !AMASK && ((k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32));
       if (need_mask) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -356,6 +390,17 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
       step(kt, slot, nx);
       kt = nx;
     }
+  } else if constexpr (AMASK) {
+    PairTiles pt(a.cq + b * a.mqs + (int64_t)tile * nkt, nkt, lane);
+    int kt = pt.next();
+    if (kt < nkt) issue(kt, 0);
+    settle(qf);
+    for (int slot = 0; kt < nkt; slot ^= 1) {
+      full = pt.full;
+      const int nx = pt.next();
+      step(kt, slot, nx);
+      kt = nx;
+    }
   } else {
     issue(0, 0);
     settle(qf);
@@ -375,12 +420,13 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
 // dK / dV: S[q][key] = Q . K^T unswapped with the wave's K^T / V^T fragments in registers,
 // dV^T = dO^T . P and dK^T = Q^T . dS from the accumulators (attention.hip); one workgroup
 // per CU, see the header for the register and LDS budget.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
 __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
   int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
-  constexpr int BUF = 4 * kTile + 1024;  // Q rows, Q tr, dO rows, dO tr, {lse, D}: 65 KiB
+  // Q rows, Q tr, dO rows, dO tr, {lse, D}: 65 KiB[, AMASK: the tile's 128 mask words: 66]
+  constexpr int BUF = 4 * kTile + 1024 + (AMASK ? 1024 : 0);
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -424,8 +470,8 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
                               : 0u;
   const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
   const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + hh * a.dsh;
-  // KMASK: the guarded copy of lse that the dQ kernel left behind D
-  const float* lse = (KMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
+  // KMASK / AMASK: the guarded copy of lse that the dQ kernel left behind D
+  const float* lse = (KMASK || AMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
                      (int64_t)bh * a.lse_stride;
   const float* Dr = a.D + (int64_t)bh * a.lse_stride;
 
@@ -461,8 +507,13 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
   // {lse, D}; a wave issues 16 x 1 KiB of tile DMA per slot.  With 512 registers the eight
   // offsets of the scalar-base form fit (at D = 64 they spilled, so that kernel forms
   // per-lane addresses always); only a tile that reaches past Sq takes the clamped path.
+  // AMASK: row `tile` of this batch element's transposed mask words, 1 KiB per query tile
+  const unsigned long long* wrow = AMASK ? a.wk + (b * a.mks + (int64_t)tile * nqt) * 128 : nullptr;
   auto issue = [&](int qt, int buf) {
     unsigned char* base = lds + buf * BUF;
+    if constexpr (AMASK) {  // two words per lane: the tile's 128 keys
+      if (wid == 1) glds16(wrow + qt * 128 + lane * 2, base + 4 * kTile + 1024);
+    }
     if (wid == 0) {  // lanes 0-15: lse[q0 .. q0+63], 16-31: D[...], 32-63: pad (lse again)
       const int seg = (lane >> 4) & 1, part = lane & 15;
       const float* src = (seg ? Dr : lse) + qt * kAKT + part * 4;
@@ -517,14 +568,33 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
         thi[dt][h][s] = tr_addr(r0 + 8, c0, lane);
       }
 
-  if (qt0 < nqt) issue(qt0, 0);
+  // AMASK: qt walks the non-dead query tiles of this key tile's row of classes (nx = the
+  // one after qt, `full` the class of qt), the ring slot alternates
+  PairTiles pt(AMASK ? a.ck + b * a.mks + (int64_t)tile * nqt : nullptr, nqt, lane);
+  [[maybe_unused]] int nx = 0, slot = 0;
+  [[maybe_unused]] bool full = false;
+  if constexpr (AMASK) {
+    nx = pt.next();
+    if (nx < nqt) issue(nx, 0);
+  } else {
+    if (qt0 < nqt) issue(qt0, 0);
+  }
   settle(kf);
   settle(vf);
-  for (int qt = qt0; qt < nqt; ++qt) {
+  for (int qt = AMASK ? nx : qt0; qt < nqt; qt = AMASK ? nx : qt + 1) {
+    if constexpr (AMASK) {
+      full = pt.full;
+      nx = pt.next();
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (qt + 1 < nqt) issue(qt + 1, (qt + 1 - qt0) & 1);
-    const unsigned char* base = lds + ((qt - qt0) & 1) * BUF;
+    if constexpr (AMASK) {
+      if (nx < nqt) issue(nx, slot ^ 1);
+    } else {
+      if (qt + 1 < nqt) issue(qt + 1, (qt + 1 - qt0) & 1);
+    }
+    const unsigned char* base = lds + (AMASK ? slot : ((qt - qt0) & 1)) * BUF;
+    if constexpr (AMASK) slot ^= 1;
     const unsigned char* Qr = base;
     const unsigned char* Qt = base + kTile;
     const unsigned char* Or = base + 2 * kTile;
@@ -579,6 +649,13 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
       }
     };
     auto mask = [&](int h, f32x16_t& sc, f32x16_t& dp) {
+      if constexpr (AMASK) {  // this lane's key against the half's 32 queries (0 past Sq)
+        const uint2 w = pair_word(base + 4 * kTile + 1024, wid * 32 + c32, hl);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!pair_bit(w, h, r)) sc[r] = dp[r] = 0.f;
+        return;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int q = q0 + 32 * h + 8 * (r >> 2) + 4 * hl + (r & 3);
@@ -602,7 +679,8 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
     // ONE straight-line block (half 1's S / dP MFMAs beside half 0's softmax VALU).
     // KMASK goes half by half, as at D = 64: with the bias and the dead-wave branch the
     // straight-line block filled all 512 registers and spilled ~70 more.
-    const bool clean = (q0 + kAKT <= Sq) && (!CAUSAL || kw0 + 31 <= q0);
+    // AMASK: a full tile is clean, a mixed one masks both halves by its bits.
+    const bool clean = AMASK ? full : (q0 + kAKT <= Sq) && (!CAUSAL || kw0 + 31 <= q0);
     if (!KMASK && clean) {
       f32x16_t sc0, dp0, sc1, dp1;
       sdp(0, sc0, dp0);
@@ -619,7 +697,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
         f32x16_t sc, dp;
         sdp(h, sc, dp);
         softmax_bwd(h, sc, dp);
-        if ((qh0 + 31 >= Sq) || (CAUSAL && kw0 + 31 > qh0)) mask(h, sc, dp);
+        if (AMASK || (qh0 + 31 >= Sq) || (CAUSAL && kw0 + 31 > qh0)) mask(h, sc, dp);
         accum(h, sc, dp);
       }
     }
@@ -639,12 +717,13 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
 // (a lane's lse / D are scalars, dQ^T = K^T . dS^T from the accumulator); it also forms
 // D = rowsum(dO * O) and, under a key mask, leaves the guarded lse and the refined D for
 // the dK/dV kernel (attention.hip).  One workgroup per CU, see the header.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
 __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
   int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
   typedef typename Frag<T>::v8 v8;
-  constexpr int BUF = 3 * kTile + (KMASK ? 1024 : 0);  // K rows, K tr, V rows[, bias]: 48 KiB
+  // K rows, K tr, V rows: 48 KiB[, KMASK: the bias; AMASK: the tile's 128 mask words]
+  constexpr int BUF = 3 * kTile + (KMASK || AMASK ? 1024 : 0);
   __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -678,7 +757,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
       of[s] = *reinterpret_cast<const v8*>(Op + 16 * s + 8 * hl);
     }
   }
-  const float lse_q = KMASK ? lse_guard(a.lse[(int64_t)bh * a.lse_stride + qq])
+  const float lse_q = KMASK || AMASK ? lse_guard(a.lse[(int64_t)bh * a.lse_stride + qq])
                             : a.lse[(int64_t)bh * a.lse_stride + qq];
   // D = rowsum(dO * O) of this lane's query from the dO fragments already in registers
   // (the two 32-lane halves hold complementary d ranges), written for the dK/dV kernel
@@ -694,7 +773,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
       for (int j = 0; j < 8; ++j) part = fmaf((float)of[s][j], (float)ov[j], part);
     }
     D_q = part + __shfl_xor(part, 32);
-    if constexpr (KMASK) {  // D itself: refined at the end; here the guarded lse
+    if constexpr (KMASK || AMASK) {  // D itself: refined at the end; here the guarded lse
       if (hl == 0 && q < Sq) a.D[((int64_t)a.B * a.H + bh) * a.lse_stride + q] = lse_q;
     } else {
       if (hl == 0 && q < Sq) a.D[(int64_t)bh * a.lse_stride + q] = D_q;
@@ -718,10 +797,15 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
   }
   // images per slot: 0 = K rows, 1 = K transposed, 2 = V rows[, bias]
   const float* kbias = KMASK ? a.kbias + (int64_t)b * kstride : nullptr;
+  // AMASK: row `tile` of this batch element's mask words, 1 KiB per key tile
+  const unsigned long long* wrow = AMASK ? a.wq + (b * a.mqs + (int64_t)tile * nkt) * 128 : nullptr;
   auto issue = [&](int kt, int buf) {
     unsigned char* base = lds + buf * BUF;
     if constexpr (KMASK) {  // lanes 0-15: bias[k0 .. k0+63], the rest pad (bias again)
       if (wid == 0) glds16(kbias + kt * kAKT + (lane & 15) * 4, base + 3 * kTile);
+    }
+    if constexpr (AMASK) {  // two words per lane: the tile's 128 queries
+      if (wid == 0) glds16(wrow + kt * 128 + lane * 2, base + 3 * kTile);
     }
     if ((kt + 1) * kAKT <= Sk) {
       const T* kb = tile_base(K, kt * kAKT, a.kss);
@@ -770,28 +854,37 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
         thi[dt][t][s] = tr_addr(r0 + 8, c0, lane);
       }
 
-  // KMASK: kt walks the live tiles only (nx = the one after kt), the ring slot alternates
+  // KMASK: kt walks the live tiles only (nx = the one after kt), the ring slot alternates;
+  // AMASK: the same over the non-dead tiles of the classes, `full` the class of kt
+  constexpr bool WALK = KMASK || AMASK;
   LiveTiles lt(KMASK ? a.klive + (int64_t)b * (kstride / kAKT) : nullptr, nkt, lane);
+  PairTiles pt(AMASK ? a.cq + b * a.mqs + (int64_t)tile * nkt : nullptr, nkt, lane);
+  [[maybe_unused]] bool full = false;
+  auto next_tile = [&]() {
+    if constexpr (AMASK) return pt.next();
+    else return lt.next();
+  };
   int nx = 0, slot = 0;
-  if constexpr (KMASK) {
-    nx = lt.next();
+  if constexpr (WALK) {
+    nx = next_tile();
     if (nx < nkt) issue(nx, 0);
   } else {
     issue(0, 0);
   }
   settle(qf);
   settle(of);
-  for (int kt = KMASK ? nx : 0; kt < nkt; kt = KMASK ? nx : kt + 1) {
-    if constexpr (KMASK) nx = lt.next();
+  for (int kt = WALK ? nx : 0; kt < nkt; kt = WALK ? nx : kt + 1) {
+    if constexpr (AMASK) full = pt.full;
+    if constexpr (WALK) nx = next_tile();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if constexpr (KMASK) {
+    if constexpr (WALK) {
       if (nx < nkt) issue(nx, slot ^ 1);
     } else {
       if (kt + 1 < nkt) issue(kt + 1, (kt + 1) & 1);
     }
-    const unsigned char* base = lds + (KMASK ? slot : (kt & 1)) * BUF;
-    if constexpr (KMASK) slot ^= 1;
+    const unsigned char* base = lds + (WALK ? slot : (kt & 1)) * BUF;
+    if constexpr (WALK) slot ^= 1;
     const unsigned char* Kr = base;
     const unsigned char* Kt = base + kTile;
     const unsigned char* Vr = base + 2 * kTile;
@@ -831,6 +924,13 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
       }
     };
     auto mask = [&](int t, f32x16_t& sc) {
+      if constexpr (AMASK) {  // this lane's query against the half's 32 keys (0 past Sk)
+        const uint2 w = pair_word(base + 3 * kTile, wid * 32 + c32, hl);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (!pair_bit(w, t, r)) sc[r] = 0.f;
+        return;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = k0 + 32 * t + (r & 3) + 8 * (r >> 2) + 4 * hl;
@@ -838,7 +938,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
       }
     };
     auto accum = [&](int t, const f32x16_t& sc) {
-      if constexpr (KMASK) {
+      if constexpr (KMASK || AMASK) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) dsum += sc[r];
       }
@@ -856,7 +956,9 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
     sdp(1, sc1, dp1);
     // wave-uniform; unmasked tiles run as one straight-line block (half 0's dQ MFMAs
     // beside half 1's softmax VALU)
-    const bool need_mask = (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
+    // (AMASK: a full tile needs none, a mixed one is masked by its bits)
+    const bool need_mask =
+        AMASK ? !full : (k0 + kAKT > Sk) || (CAUSAL && k0 + kAKT - 1 > qb0 + wid * 32);
     if (!need_mask) {
       dsoft(0, sc0, dp0);
       accum(0, sc0);
@@ -871,7 +973,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
       accum(1, sc1);
     }
   }
-  if constexpr (KMASK) {
+  if constexpr (KMASK || AMASK) {
     const float dD = dsum + __shfl_xor(dsum, 32);  // the two halves hold 32 keys each per tile
     if (hl == 0 && q < Sq) a.D[(int64_t)bh * a.lse_stride + q] = D_q + dD;
   }
@@ -887,6 +989,12 @@ void attn_fwd_d128(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
   AttnArgs a = kernel_args<AttnArgs>("attn_fwd", p);
   a.o = o; a.lse = lse;
   dim3 grid((p.Sq + 127) / 128, p.B * p.H), block(kAT);
+  if (p.wq != nullptr) {
+    dispatch_amask(p, a.thr8 != 0, [&](auto t, auto d) {
+      hipLaunchKernelGGL((ATTN_AMASK_KERNEL(attn128_fwd_k)), grid, block, 0, st, a);
+    });
+    return;
+  }
   dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m, auto vl) {
     hipLaunchKernelGGL((ATTN_KERNEL(attn128_fwd_k)), grid, block, 0, st, a);
   });
@@ -896,11 +1004,19 @@ void attn_bwd_d128(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
   AttnBwdArgs a = bwd_kernel_args("attn_bwd", p, g);
   // dQ owns 128-query tiles, dK/dV 128-key tiles; dQ first (it writes D), then dK/dV
   dim3 qgrid((p.Sq + 127) / 128, p.B * p.H), kgrid((p.Sk + 127) / 128, p.B * p.H), block(kAT);
+  if (p.wq != nullptr) {
+    dispatch_amask(p, a.thr8 != 0, [&](auto t, auto d) {
+      hipLaunchKernelGGL((ATTN_AMASK_KERNEL(attn128_bwd_dq_k)), qgrid, block, 0, st, a);
+      hipLaunchKernelGGL((ATTN_AMASK_KERNEL(attn128_bwd_dkdv_k)), kgrid, block, 0, st, a);
+    });
+    return;
+  }
   dispatch(p, a.thr8 != 0, [&](auto t, auto c, auto d, auto m, auto vl) {
     hipLaunchKernelGGL((ATTN_KERNEL(attn128_bwd_dq_k)), qgrid, block, 0, st, a);
     hipLaunchKernelGGL((ATTN_KERNEL(attn128_bwd_dkdv_k)), kgrid, block, 0, st, a);
   });
 }
 #undef ATTN_KERNEL
+#undef ATTN_AMASK_KERNEL
 
 }  // namespace amd

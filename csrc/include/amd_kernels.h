@@ -525,6 +525,13 @@ struct AttnProblem {
   // (no host copy).  No key mask.  Lengths are clipped to max_seqlen and to T on the device.
   const int32_t* cu_seqlens = nullptr;
   int T = 0;  // rows of the packed views
+  // Prepared pair mask (attn_prepare_pair_mask) of the Sq x Sk (query, key) pairs, all null
+  // = none; with one, no causal flag, key mask or cu_seqlens (the bits hold those shapes).
+  const unsigned long long* wq = nullptr;  // [Bm][ceil(Sq/128)][ceil(Sk/64)][128] bit words
+  const unsigned char* cq = nullptr;       // [Bm][ceil(Sq/128)][ceil(Sk/64)] tile classes
+  const unsigned long long* wk = nullptr;  // [Bm][ceil(Sk/128)][ceil(Sq/64)][128], transposed
+  const unsigned char* ck = nullptr;       // [Bm][ceil(Sk/128)][ceil(Sq/64)]
+  int64_t pm_sb = 0;  // batch stride of cq in tiles; 0: one mask shared by the batch (Bm = 1)
 };
 // Row stride of lse / D (S = Sq) and of the prepared key mask (S = Sk): S rounded up to
 // a multiple of 64.
@@ -540,6 +547,17 @@ void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st);
 enum class AttnMaskKind : int { Bool8 = 0, F32 = 1, F16 = 2, BF16 = 3 };
 void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, float* bias,
                            unsigned char* live, hipStream_t st);
+
+// Boolean (query, key) mask -> bit tiles (attention_pairmask.hip).  mask: bytes [Sq][Sk]
+// (mask_sb = 0) or [B][Sq][Sk] (mask_sb = Sq * Sk), non-zero = masked; kpm: optional bytes
+// [B][Sk], non-zero = masked key, OR-ed in.  Bm = B masks come out when mask_sb != 0 or kpm
+// is given, else one.  wq word (qt, kt, r): bit j set = query 128 qt + r attends key
+// 64 kt + j; wk word (kt, qt, r): bit i set = query 64 qt + i attends key 128 kt + r; bits
+// past Sq or Sk are 0.  cq / ck: 0 = no bit of the tile set, 2 = all set, 1 = mixed.  One
+// launch, no host sync.
+void attn_prepare_pair_mask(const unsigned char* mask, int64_t mask_sb, const unsigned char* kpm,
+                            int Bm, int Sq, int Sk, unsigned long long* wq, unsigned char* cq,
+                            unsigned long long* wk, unsigned char* ck, hipStream_t st);
 
 // backward, two launches and no atomics: the dQ kernel first (ceil(Sq/128) tiles), which
 // also writes D = rowsum(dO*O) and, under a key mask, the guarded copy of lse behind it;

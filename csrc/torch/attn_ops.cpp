@@ -87,6 +87,33 @@ void check_key_mask(const c10::optional<at::Tensor>& bias, const c10::optional<a
   *pl = kl.data_ptr<unsigned char>();
 }
 
+// the prepared pair mask of attn_prepare_attn_mask_op for a call's (B, Sq, Sk), shared
+// (leading dim 1) or per batch element
+void check_pair_mask(const at::Tensor& wq, const at::Tensor& cq, const at::Tensor& wk,
+                     const at::Tensor& ck, const at::Tensor& q, AttnProblem& L) {
+  const int64_t nq128 = (L.Sq + 127) / 128, nq64 = (L.Sq + 63) / 64;
+  const int64_t nk128 = (L.Sk + 127) / 128, nk64 = (L.Sk + 63) / 64;
+  const int64_t Bm = cq.dim() == 3 ? cq.size(0) : -1;
+  TORCH_CHECK(Bm == 1 || Bm == L.B, "attn: the pair mask must be shared or hold B = ", L.B,
+              " masks, got cq ", cq.sizes());
+  auto ok = [&](const at::Tensor& t, at::ScalarType ty, std::initializer_list<int64_t> shape) {
+    const bool word = t.scalar_type() == at::kUInt64 || t.scalar_type() == at::kLong;
+    return t.is_cuda() && t.device() == q.device() && (ty == at::kLong ? word : t.scalar_type() == ty) &&
+           t.sizes() == at::IntArrayRef(shape) && t.is_contiguous() &&
+           (ty != at::kLong || ((uintptr_t)t.data_ptr() % 16) == 0);  // the words are DMA'd
+  };
+  TORCH_CHECK(ok(wq, at::kLong, {Bm, nq128, nk64, 128}) && ok(cq, at::kByte, {Bm, nq128, nk64}) &&
+                  ok(wk, at::kLong, {Bm, nk128, nq64, 128}) && ok(ck, at::kByte, {Bm, nk128, nq64}),
+              "attn: not the prepared pair mask (attn.prepare_attn_mask) of Sq = ", L.Sq,
+              ", Sk = ", L.Sk, " on q's device: wq ", wq.sizes(), ", cq ", cq.sizes(), ", wk ",
+              wk.sizes(), ", ck ", ck.sizes());
+  L.wq = static_cast<const unsigned long long*>(wq.data_ptr());
+  L.wk = static_cast<const unsigned long long*>(wk.data_ptr());
+  L.cq = cq.data_ptr<unsigned char>();
+  L.ck = ck.data_ptr<unsigned char>();
+  L.pm_sb = Bm == 1 ? 0 : nq128 * nk64;
+}
+
 // ---- packed variable-length sequences: [T, H, D] views and an int32 offsets vector
 bool view3_ok(const at::Tensor& t) {
   return t.stride(2) == 1 && ((uintptr_t)t.data_ptr() % 16) == 0 && t.stride(0) % 8 == 0 &&
@@ -171,6 +198,74 @@ std::tuple<at::Tensor, at::Tensor> attn_prepare_key_mask_op(at::Tensor mask, int
   return {bias, live};
 }
 
+std::tuple<at::Tensor, at::Tensor> attn_prepare_attn_mask_op(
+    at::Tensor mask, c10::optional<at::Tensor> key_padding_mask) {
+  c10::NoGradGuard no_grad_;
+  auto bytes = [](const at::Tensor& t) {
+    return t.scalar_type() == at::kBool || t.scalar_type() == at::kByte;
+  };
+  TORCH_CHECK(mask.is_cuda() && bytes(mask) && (mask.dim() == 2 || mask.dim() == 3) &&
+                  mask.is_contiguous(),
+              "attn.prepare_attn_mask: a contiguous bool / uint8 [Sq, Sk] or [B, Sq, Sk] GPU "
+              "mask expected (non-zero = masked), got ", mask.scalar_type(), " ", mask.sizes());
+  const int64_t Sq = mask.size(-2), Sk = mask.size(-1);
+  TORCH_CHECK(Sq > 0 && Sk > 0 && Sq < (int64_t{1} << 24) && Sk < (int64_t{1} << 24),
+              "attn.prepare_attn_mask: Sq, Sk must be in (0, 2^24), got ", mask.sizes());
+  int64_t Bm = mask.dim() == 3 ? mask.size(0) : 1;
+  const unsigned char* kpm = nullptr;
+  if (key_padding_mask.has_value()) {
+    const at::Tensor& kp = *key_padding_mask;
+    TORCH_CHECK(kp.is_cuda() && kp.device() == mask.device() && bytes(kp) && kp.dim() == 2 &&
+                    kp.size(1) == Sk && kp.is_contiguous() &&
+                    (mask.dim() == 2 || kp.size(0) == Bm),
+                "attn.prepare_attn_mask: key_padding_mask must be a contiguous bool / uint8 "
+                "[B, Sk] tensor on the mask's device, got ", kp.scalar_type(), " ", kp.sizes());
+    Bm = kp.size(0);
+    kpm = static_cast<const unsigned char*>(kp.data_ptr());
+  }
+  TORCH_CHECK(Bm <= 65535, "attn.prepare_attn_mask: at most 65535 masks, got ", Bm);
+  const int64_t nq128 = (Sq + 127) / 128, nq64 = (Sq + 63) / 64;
+  const int64_t nk128 = (Sk + 127) / 128, nk64 = (Sk + 63) / 64;
+  // one int64 buffer {wq, wk} and one uint8 buffer {cq, ck}; the Python side views them
+  at::Tensor words = at::empty({Bm * 128 * (nq128 * nk64 + nk128 * nq64)},
+                               mask.options().dtype(at::kLong));
+  at::Tensor cls = at::empty({Bm * (nq128 * nk64 + nk128 * nq64)}, mask.options().dtype(at::kByte));
+  if (Bm > 0) {
+    auto* w = reinterpret_cast<unsigned long long*>(words.data_ptr<int64_t>());
+    unsigned char* c = cls.data_ptr<unsigned char>();
+    attn_prepare_pair_mask(static_cast<const unsigned char*>(mask.data_ptr()),
+                           mask.dim() == 3 ? Sq * Sk : 0, kpm, (int)Bm, (int)Sq, (int)Sk, w, c,
+                           w + Bm * 128 * nq128 * nk64, c + Bm * nq128 * nk64, cur_stream());
+  }
+  return {words, cls};
+}
+
+namespace {
+std::tuple<at::Tensor, at::Tensor> run_fwd(AttnProblem& L, const at::Tensor& q);
+void run_bwd(AttnProblem& F, at::Tensor dout, const at::Tensor& q, const at::Tensor& k,
+             at::Tensor o, at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv);
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor> attn_fwd_amask_op(at::Tensor q, at::Tensor k, at::Tensor v,
+                                                     double dropout, int64_t seed, double scale,
+                                                     at::Tensor wq, at::Tensor cq, at::Tensor wk,
+                                                     at::Tensor ck) {
+  c10::NoGradGuard no_grad_;
+  AttnProblem L = make_launch(q, k, v, false, dropout, seed, scale);
+  check_pair_mask(wq, cq, wk, ck, q, L);
+  return run_fwd(L, q);
+}
+
+void attn_bwd_amask_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                       at::Tensor lse, double dropout, int64_t seed, double scale, at::Tensor dq,
+                       at::Tensor dk, at::Tensor dv, at::Tensor wq, at::Tensor cq, at::Tensor wk,
+                       at::Tensor ck) {
+  c10::NoGradGuard no_grad_;
+  AttnProblem F = make_launch(q, k, v, false, dropout, seed, scale);
+  check_pair_mask(wq, cq, wk, ck, q, F);
+  run_bwd(F, dout, q, k, o, lse, dq, dk, dv);
+}
+
 std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::Tensor v,
                                                bool causal, double dropout, int64_t seed,
                                                double scale, c10::optional<at::Tensor> key_bias,
@@ -178,6 +273,12 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
   c10::NoGradGuard no_grad_;
   AttnProblem L = make_launch(q, k, v, causal, dropout, seed, scale);
   check_key_mask(key_bias, key_live, q, L.B, L.Sk, &L.kbias, &L.klive);
+  return run_fwd(L, q);
+}
+
+namespace {
+// the forward of a checked problem: allocation, the empty cases, the launch
+std::tuple<at::Tensor, at::Tensor> run_fwd(AttnProblem& L, const at::Tensor& q) {
   const int Sp = attn_lse_stride(L.Sq);
   at::Tensor o = at::empty({L.B, L.Sq, L.H, L.D}, q.options());
   at::Tensor lse = at::empty({L.B, L.H, Sp}, q.options().dtype(at::kFloat));
@@ -189,6 +290,7 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_op(at::Tensor q, at::Tensor k, at::T
   }
   return {o, Sp == L.Sq ? lse : lse.narrow(2, 0, L.Sq)};
 }
+}  // namespace
 
 void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
                  at::Tensor lse, bool causal, double dropout, int64_t seed, double scale,
@@ -197,6 +299,13 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   c10::NoGradGuard no_grad_;
   AttnProblem F = make_launch(q, k, v, causal, dropout, seed, scale);
   check_key_mask(key_bias, key_live, q, F.B, F.Sk, &F.kbias, &F.klive);
+  run_bwd(F, dout, q, k, o, lse, dq, dk, dv);
+}
+
+namespace {
+// the backward of a checked problem: the buffers' checks, the workspace, the launches
+void run_bwd(AttnProblem& F, at::Tensor dout, const at::Tensor& q, const at::Tensor& k,
+             at::Tensor o, at::Tensor lse, at::Tensor dq, at::Tensor dk, at::Tensor dv) {
   if (!(dout.dim() == 4 && view_ok(dout))) dout = dout.contiguous();
   if (!(o.dim() == 4 && view_ok(o))) o = o.contiguous();
   AttnBwd G;
@@ -228,7 +337,7 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
     lse = padded;
   }
   // masked: D is followed by the dQ kernel's guarded copy of lse for the dK/dV kernel
-  at::Tensor D = at::empty({F.kbias ? 2 : 1, B, H, Sp}, lse.options());
+  at::Tensor D = at::empty({F.kbias || F.wq ? 2 : 1, B, H, Sp}, lse.options());
   if (B * H == 0) return;
   if (F.Sk == 0) {  // no key: nothing reaches q
     dq.zero_();
@@ -243,6 +352,7 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
   G.D = D.data_ptr<float>();
   attn_bwd(F, G, cur_stream());
 }
+}  // namespace
 
 std::tuple<at::Tensor, at::Tensor> attn_fwd_varlen_op(at::Tensor q, at::Tensor k, at::Tensor v,
                                                       at::Tensor cu_seqlens, int64_t max_seqlen,

@@ -36,6 +36,27 @@ void attn_bwd_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::
                  c10::optional<at::Tensor> key_bias = c10::nullopt,
                  c10::optional<at::Tensor> key_live = c10::nullopt);
 
+// Boolean pair mask: bool / uint8 [Sq, Sk] or [B, Sq, Sk] (non-zero = masked), optionally
+// OR-ed with a bool / uint8 [B, Sk] key-padding mask (the result is then per batch) -> the
+// bit tiles of csrc/hip/attention_pairmask.hip as two flat buffers: int64 words {wq
+// [Bm][ceil(Sq/128)][ceil(Sk/64)][128], wk [Bm][ceil(Sk/128)][ceil(Sq/64)][128]} and uint8
+// classes {cq [Bm][ceil(Sq/128)][ceil(Sk/64)], ck [Bm][ceil(Sk/128)][ceil(Sq/64)]}.  One
+// launch, no host sync; serves every layer that shares the mask, forward and backward.
+std::tuple<at::Tensor, at::Tensor> attn_prepare_attn_mask_op(
+    at::Tensor mask, c10::optional<at::Tensor> key_padding_mask = c10::nullopt);
+
+// attn_fwd_op / attn_bwd_op under a prepared pair mask (no causal flag, no key mask: the
+// bits hold both).  A query with no set bit gets o = 0, lse = -inf, dq = 0; a key nobody
+// attends gets dk = dv = 0.
+std::tuple<at::Tensor, at::Tensor> attn_fwd_amask_op(at::Tensor q, at::Tensor k, at::Tensor v,
+                                                     double dropout, int64_t seed, double scale,
+                                                     at::Tensor wq, at::Tensor cq, at::Tensor wk,
+                                                     at::Tensor ck);
+void attn_bwd_amask_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+                       at::Tensor lse, double dropout, int64_t seed, double scale, at::Tensor dq,
+                       at::Tensor dk, at::Tensor dv, at::Tensor wq, at::Tensor cq, at::Tensor wk,
+                       at::Tensor ck);
+
 // Packed variable-length sequences.  q, k, v: [T, H, 64] bf16/fp16 views of the real
 // tokens of B sequences (head dim contiguous, 16-B aligned rows, any token / head strides,
 // one T, H and dtype); cu_seqlens: contiguous int32 [B + 1] on q's device, read by the

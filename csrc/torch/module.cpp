@@ -109,6 +109,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
            py::arg("key_bias") = py::none(), py::arg("key_live") = py::none());
   attn.def("prepare_key_mask", &attn_prepare_key_mask_op, py::arg("mask"), py::arg("S"));
+  attn.def("prepare_attn_mask", &attn_prepare_attn_mask_op, py::arg("mask"),
+           py::arg("key_padding_mask") = py::none());
+  attn.def("fwd_amask", &attn_fwd_amask_op, py::arg("q"), py::arg("k"), py::arg("v"),
+           py::arg("dropout"), py::arg("seed"), py::arg("scale"), py::arg("wq"), py::arg("cq"),
+           py::arg("wk"), py::arg("ck"));
+  attn.def("bwd_amask", &attn_bwd_amask_op, py::arg("dout"), py::arg("q"), py::arg("k"),
+           py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("dropout"), py::arg("seed"),
+           py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("wq"),
+           py::arg("cq"), py::arg("wk"), py::arg("ck"));
   attn.def("fwd_varlen", &attn_fwd_varlen_op, py::arg("q"), py::arg("k"), py::arg("v"),
            py::arg("cu_seqlens"), py::arg("max_seqlen"), py::arg("causal"), py::arg("dropout"),
            py::arg("seed"), py::arg("scale"));

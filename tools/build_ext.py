@@ -35,7 +35,10 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # is not measured (docs/PERF.md).  The other files keep their flags: their code and
 # recorded numbers do not move.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-HIP_EXTRA = {"attention_d128.hip": _NO_PK_F32}
+HIP_EXTRA = {"attention_d128.hip": _NO_PK_F32, "attention_pairmask.hip": _NO_PK_F32}
+# Sources that include another source: attention_pairmask.hip instantiates the head dim 64
+# kernel templates of attention.hip under its own flags.
+HIP_INCLUDES = {"attention_pairmask.hip": ["attention.hip"]}
 
 
 def _torch_paths():
@@ -117,7 +120,10 @@ def build(jobs: int | None = None, verbose: bool = False, clean: bool = False) -
     for s in hip_srcs + cpp_srcs:
         o = _obj_for(s)
         objs.append(o)
-        if (not os.path.exists(o)) or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_t):
+        deps = [s] + [os.path.join(os.path.dirname(s), d)
+                      for d in HIP_INCLUDES.get(os.path.basename(s), [])]
+        if (not os.path.exists(o)) or os.path.getmtime(o) < max(
+                hdr_t, *(os.path.getmtime(d) for d in deps)):
             todo.append((s, o, hip_cmd(s, o) if s.endswith(".hip") else cpp_cmd(s, o)))
 
     jobs = jobs or min(8, os.cpu_count() or 4)

@@ -7,6 +7,7 @@
     python tools/microbench.py ln      # FusedLayerNorm fwd/bwd vs torch LayerNorm
     python tools/microbench.py lamb    # FusedLAMB / FusedAdam on BERT-large's 336M params
     python tools/microbench.py attn-packed  # packed (cu_seqlens) vs padded + key mask attention
+    python tools/microbench.py attn-pairmask  # boolean [S, S] masks vs SDPA and the causal kernels
 """
 from __future__ import annotations
 
@@ -553,6 +554,81 @@ def bench_attn(args):
                 flush=True)
     bench_attn_packed(args)
     bench_attn_d128(args)
+    bench_attn_pairmask(args)
+
+
+def bench_attn_pairmask(args):
+    """Boolean [S, S] pair masks (fwd_amask / bwd_amask on the bit tiles of
+    csrc/hip/attention_pairmask.hip), bf16 forward + backward at D = 64 and 128: a
+    lower-triangular mask at 8 x 16 x 1024 against (a) SDPA with the same boolean mask, the
+    path such a call took before, and (b) the causal=True kernels, the same work without bit
+    tests; a sliding window of 256 at 4 x 16 x 4096 against SDPA with the mask.  Variants are
+    timed alternately over ROUNDS rounds; median and spread (max - min) / median."""
+    from apex_example_amd import _native
+    from apex_example_amd.ops.attention import prepare_attn_mask
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    A = _native.require().attn
+    print("| shape (B x H x S) | D | variant | fwd us | bwd us | fwd + bwd us | spread |")
+    print("|---|---|---|---|---|---|---|")
+    idx = lambda s_: (torch.arange(s_, device=dev).view(s_, 1),  # noqa: E731
+                      torch.arange(s_, device=dev).view(1, s_))
+    tril = lambda i, j: j > i                                    # noqa: E731
+    window = lambda i, j: (j > i) | (i - j >= 256)               # noqa: E731
+    for name, b, h, s_, masked, causal_twin in [("8 x 16 x 1024 tril", 8, 16, 1024, tril, True),
+                                                ("4 x 16 x 4096 window 256", 4, 16, 4096, window,
+                                                 False)]:
+        for d in (64, 128):
+            sc = 1.0 / d ** 0.5
+            mask = masked(*idx(s_))  # True = masked pair
+            m = prepare_attn_mask(mask)
+            pm = (m.wq, m.cq, m.wk, m.ck)
+            q, k, v, do = (torch.randn(b, s_, h, d, device=dev, dtype=dt) for _ in range(4))
+            dq, dk, dv = (torch.empty_like(t) for t in (q, k, v))
+            o, lse = A.fwd_amask(q, k, v, 0.0, 0, sc, *pm)
+            oc, lsec = A.fwd(q, k, v, True, 0.0, 0, sc)
+            sq, sk, sv = (t.transpose(1, 2).contiguous().requires_grad_(True) for t in (q, k, v))
+            sdo, keep = do.transpose(1, 2).contiguous(), ~mask  # SDPA: True = attend
+
+            def pair():
+                return (lambda: A.fwd_amask(q, k, v, 0.0, 0, sc, *pm),
+                        lambda: A.bwd_amask(do, q, k, v, o, lse, 0.0, 0, sc, dq, dk, dv, *pm))
+
+            def causal():
+                return (lambda: A.fwd(q, k, v, True, 0.0, 0, sc),
+                        lambda: A.bwd(do, q, k, v, oc, lsec, True, 0.0, 0, sc, dq, dk, dv))
+
+            def sdpa():
+                f = lambda: F.scaled_dot_product_attention(sq, sk, sv, attn_mask=keep)  # noqa: E731
+                so = f()
+                return f, lambda: torch.autograd.grad(so, (sq, sk, sv), sdo, retain_graph=True)
+
+            variants = [("gfx950 pair mask", pair), ("sdpa bool mask", sdpa)]
+            if causal_twin:
+                variants.append(("gfx950 causal=True", causal))
+            t_end = time.time() + 2.0  # clock / first-use ramp, as in bench_attn
+            while time.time() < t_end:
+                for fn in pair():
+                    fn()
+                torch.cuda.synchronize()
+            times = {n: [] for n, _ in variants}
+            for _ in range(ROUNDS):
+                for n, make in variants:
+                    try:
+                        f, bw = make()
+                        times[n].append((timeit(f, iters=20, warmup=5),
+                                         timeit(bw, iters=20, warmup=5)))
+                    except Exception as e:  # noqa: BLE001
+                        print("%s %s failed: %s" % (n, name, str(e)[:200]))
+            med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+            for n, _ in variants:
+                if len(times[n]) < ROUNDS:
+                    continue
+                tot = [tf_ + tb for tf_, tb in times[n]]
+                print("| %s | %d | %s | %.0f | %.0f | %.0f | %.1f %% |" % (
+                    name, d, n, med([tf_ for tf_, _ in times[n]]),
+                    med([tb for _, tb in times[n]]), med(tot),
+                    100 * (max(tot) - min(tot)) / med(tot)), flush=True)
 
 
 def bench_attn_d128(args):
@@ -934,12 +1010,13 @@ def bench_conv1x1_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
-                             "attn", "attn-packed", "attn-d128"])
+                             "attn", "attn-packed", "attn-d128", "attn-pairmask"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
      "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn,
-     "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128}[a.what](a)
+     "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128,
+     "attn-pairmask": bench_attn_pairmask}[a.what](a)
 
 
 if __name__ == "__main__":
