@@ -28,6 +28,9 @@ class GPT2Config:
     n_embd: int = 1024
     n_layer: int = 24
     n_head: int = 16
+    # key/value heads shared by n_head // n_kv_head query heads each (grouped-query attention;
+    # 1 = multi-query).  None: n_head of them, the GPT-2 module and state dict as published.
+    n_kv_head: int | None = None
     resid_pdrop: float = 0.1
     embd_pdrop: float = 0.1
     attn_pdrop: float = 0.1
@@ -52,7 +55,12 @@ class GPT2Attention(nn.Module):
         super().__init__()
         self.h = cfg.n_head
         self.d = cfg.n_embd // cfg.n_head
-        self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd)
+        self.hkv = cfg.n_kv_head
+        if self.hkv is not None and (self.hkv <= 0 or self.h % self.hkv != 0):
+            raise ValueError("n_head = %d does not split over n_kv_head = %d" % (self.h, self.hkv))
+        # grouped: one projection to [query heads | key heads | value heads]
+        self.c_attn = nn.Linear(cfg.n_embd, 3 * cfg.n_embd if self.hkv is None
+                                else (self.h + 2 * self.hkv) * self.d)
         self.c_proj = nn.Linear(cfg.n_embd, cfg.n_embd)
         self.p = cfg.attn_pdrop
         self.resid_dropout = nn.Dropout(cfg.resid_pdrop)
@@ -65,6 +73,8 @@ class GPT2Attention(nn.Module):
     def forward(self, x, resid_dropout=True):
         b, s, e = x.shape
         drop = self.resid_dropout if resid_dropout else (lambda t: t)
+        if self.hkv is not None:
+            return drop(self._lin(self.c_proj, self._grouped(x)))
         qkv = self._lin(self.c_attn, x).view(b, s, 3, self.h, self.d)
         p = self.p if self.training else 0.0
         if self.fused and fused_attn.supported(qkv, self.d):
@@ -74,6 +84,21 @@ class GPT2Attention(nn.Module):
         o = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2], is_causal=True, dropout_p=p)
         o = o.transpose(1, 2).reshape(b, s, e)
         return drop(self._lin(self.c_proj, o))
+
+
+    def _grouped(self, x):
+        """Attention output [b, s, e] with n_kv_head key/value heads."""
+        b, s, e = x.shape
+        h, hkv = self.h, self.hkv
+        qkv = self._lin(self.c_attn, x).view(b, s, h + 2 * hkv, self.d)
+        p = self.p if self.training else 0.0
+        if self.fused and fused_attn.supported(qkv, self.d):
+            return fused_attn.fused_attention_qkv_gqa(qkv, hkv, causal=True,
+                                                      dropout_p=p).view(b, s, e)
+        q, k, v = (t.transpose(1, 2) for t in qkv.split((h, hkv, hkv), 2))
+        k, v = (t.repeat_interleave(h // hkv, 1) for t in (k, v))
+        o = F.scaled_dot_product_attention(q, k, v, is_causal=True, dropout_p=p)
+        return o.transpose(1, 2).reshape(b, s, e)
 
 
 class GPT2MLP(nn.Module):

@@ -49,8 +49,19 @@ output of a fused QKV projection and returns one dqkv of its layout.  The result
 those of the padded call with a key-padding mask, read at the real rows; not combined
 with key masks or unequal query / key lengths.
 
+Grouped-query and multi-query heads: k and v (and a packed kv) may have Hkv < H heads with
+H % Hkv == 0; query head h reads key/value head h // (H // Hkv) (torch's ``enable_gqa``,
+the Llama / Megatron layout), without expanding K / V: the dK/dV kernel walks the query heads
+of a group and writes each dK / dV row once (csrc/hip/attention_gqa.hip).
+``fused_attention_qkv_gqa(qkv, num_kv_heads)`` takes the [B, S, H + 2 Hkv, D] output of one
+fused projection (query heads, then key heads, then value heads) and returns one dqkv of
+that layout.  The dropout mask is that of the same call on K / V expanded to H heads.  Not
+combined with ``attn_mask`` or packed sequences (ValueError).  docs/PERF.md, "Attention:
+grouped-query heads".
+
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
-batch size and head count (the query and key lengths may differ), no mask other than
+batch size (the query and key lengths may differ) and H query heads over Hkv key/value heads
+with H % Hkv == 0 (Hkv < H neither with a pair mask nor packed), no mask other than
 a per-batch key mask, a boolean pair mask (an additive [Tq, Tk] ``attn_mask`` is not
 fused) or, at equal lengths, the causal mask; packed sequences ([T, H, D] with ``cu_seqlens``): q, k and v of one token
 and head count, self-attention per sequence, optional causal mask, no key mask.  Callers
@@ -267,9 +278,30 @@ _SPLIT = {
 }
 
 
+def _split(layout, ts):
+    """The (q, k, v) views of the tensors ``ts`` under ``layout``: a key of ``_SPLIT`` or
+    ("gqa_qkv", Hkv), one qkv [B, S, H + 2 Hkv, D] with the query heads first, then the key
+    heads, then the value heads."""
+    if isinstance(layout, tuple):
+        hkv = layout[1]
+        return ts[0].split((ts[0].size(2) - 2 * hkv, hkv, hkv), 2)
+    return _SPLIT[layout](ts)
+
+
+def _check_heads(q, k, excluded=None):
+    """ValueError for H query heads that do not split over k's Hkv heads (dim -2 of both)
+    or, with ``excluded`` naming an argument they are not combined with, for Hkv < H."""
+    H, Hkv = q.size(-2), k.size(-2)
+    if Hkv <= 0 or H % Hkv != 0:
+        raise ValueError("%d query heads do not split over %d key/value heads" % (H, Hkv))
+    if excluded is not None and Hkv != H:
+        raise ValueError("grouped-query heads (H = %d, Hkv = %d) are not combined with %s: "
+                         "expand k / v to H heads for that" % (H, Hkv, excluded))
+
+
 class AttentionFunction(torch.autograd.Function):
     """o = softmax(q k^T * scale [+ key bias] [+ causal mask]) [dropout] v -> [B, Sq, H, D]
-    on the q / k / v views of ``inputs`` (any strides) under ``layout``, a key of ``_SPLIT``;
+    on the q / k / v views of ``inputs`` (any strides) under ``layout`` (``_split``);
     (kbias, klive) is a prepared key mask of the Sk keys or (None, None).  ``varlen`` is
     None or, with the "varlen_*" layouts ([T, H, D] views of packed sequences, o
     [T, H, D]), the pair (cu_seqlens int32 [B + 1], max_seqlen); it rides in ``ctx``
@@ -282,7 +314,7 @@ class AttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layout, causal, dropout_p, scale, seed, kbias, klive, varlen, *inputs):
-        q, k, v = _SPLIT[layout](inputs)
+        q, k, v = _split(layout, inputs)
         ctx.cfg = (layout, bool(causal), float(dropout_p), int(seed), float(scale))
         ctx.varlen = varlen
         if varlen is None:
@@ -304,15 +336,15 @@ class AttentionFunction(torch.autograd.Function):
         else:
             grads = [torch.empty_like(t) for t in inputs]
         if ctx.varlen is None:
-            _C().bwd(do, *_SPLIT[layout](inputs), o, lse, *cfg, *_SPLIT[layout](grads), kbias,
+            _C().bwd(do, *_split(layout, inputs), o, lse, *cfg, *_split(layout, grads), kbias,
                      klive)
         elif isinstance(ctx.varlen, PreparedAttnMask):
             m = ctx.varlen
-            _C().bwd_amask(do, *_SPLIT[layout](inputs), o, lse, *cfg[1:],
-                           *_SPLIT[layout](grads), m.wq, m.cq, m.wk, m.ck)
+            _C().bwd_amask(do, *_split(layout, inputs), o, lse, *cfg[1:],
+                           *_split(layout, grads), m.wq, m.cq, m.wk, m.ck)
         else:
-            _C().bwd_varlen(do, *_SPLIT[layout](inputs), o, lse, *ctx.varlen, *cfg,
-                            *_SPLIT[layout](grads))
+            _C().bwd_varlen(do, *_split(layout, inputs), o, lse, *ctx.varlen, *cfg,
+                            *_split(layout, grads))
         return (None,) * 8 + tuple(grads)
 
 
@@ -340,8 +372,10 @@ class FusedKVAttentionFunction:
 
 def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_padding_mask=None,
                     key_bias=None, attn_mask=None):
-    """q: [B, Sq, H, D], k, v: [B, Sk, H, D] -> o [B, Sq, H, D] (Sq != Sk is
-    cross-attention; ``causal`` needs Sq == Sk).  key_padding_mask: [B, Sk] bool, True =
+    """q: [B, Sq, H, D], k, v: [B, Sk, Hkv, D] -> o [B, Sq, H, D] (Sq != Sk is
+    cross-attention; ``causal`` needs Sq == Sk; Hkv < H with H % Hkv == 0 is grouped-query
+    attention, query head h reading key/value head h // (H // Hkv), not under ``attn_mask``).
+    key_padding_mask: [B, Sk] bool, True =
     masked key; key_bias: [B, Sk] float, added to the scaled scores; either may be a
     ``PreparedKeyMask``.  attn_mask: bool [Sq, Sk] / [B, Sq, Sk], True = masked pair, or a
     ``PreparedAttnMask``; it excludes ``causal`` and ``key_bias`` and merges a boolean
@@ -349,6 +383,7 @@ def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_paddin
     _check_causal(causal, q.size(1), k.size(1))
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
     if attn_mask is not None:
+        _check_heads(q, k, "attn_mask")
         m = _attn_mask(attn_mask, causal, key_padding_mask, key_bias, q, k)
         return AttentionFunction.apply("qkv", False, dropout_p, scale, _seed(dropout_p), None,
                                        None, m, q, k, v)
@@ -359,11 +394,13 @@ def fused_attention(q, k, v, causal=False, dropout_p=0.0, scale=None, key_paddin
 
 def fused_attention_kv(q, kv, dropout_p=0.0, scale=None, key_padding_mask=None, key_bias=None,
                        attn_mask=None):
-    """q: [B, Sq, H, D], kv: [B, Sk, 2, H, D] (the packed output of a fused KV
+    """q: [B, Sq, H, D], kv: [B, Sk, 2, Hkv, D] (the packed output of a fused KV
     projection, any strides) -> o [B, Sq, H, D]; the backward writes dK and dV into one
-    packed dkv of kv's layout.  Masks as in ``fused_attention``."""
+    packed dkv of kv's layout.  Masks and Hkv as in ``fused_attention``."""
     if kv.dim() != 5 or kv.size(2) != 2:
         raise ValueError("kv must be [B, Sk, 2, H, D], got %s" % (tuple(kv.shape),))
+    if attn_mask is not None:
+        _check_heads(q, kv, "attn_mask")
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
     if attn_mask is not None:
         m = _attn_mask(attn_mask, False, key_padding_mask, key_bias, q, kv)
@@ -386,6 +423,27 @@ def fused_attention_qkv(qkv, causal=False, dropout_p=0.0, scale=None, key_paddin
     kbias, klive = _key_mask(key_padding_mask, key_bias, qkv)
     return FusedQKVAttentionFunction.apply(qkv, causal, dropout_p, scale, _seed(dropout_p),
                                            kbias, klive)
+
+
+def fused_attention_qkv_gqa(qkv, num_kv_heads, causal=False, dropout_p=0.0, scale=None,
+                            key_padding_mask=None, key_bias=None):
+    """qkv: [B, S, H + 2 Hkv, D] with Hkv = ``num_kv_heads`` (the output of one fused
+    projection: H query heads, then Hkv key heads, then Hkv value heads; any strides,
+    sequence-first included) -> o [B, S, H, D]; query head h reads key/value head
+    h // (H // Hkv).  The backward returns one packed dqkv of qkv's layout.  Key masks as in
+    ``fused_attention``.  With Hkv == H the results are bitwise those of
+    ``fused_attention_qkv`` on the same data."""
+    hkv = int(num_kv_heads)
+    if qkv.dim() != 4 or hkv <= 0 or qkv.size(2) <= 2 * hkv:
+        raise ValueError("qkv must be [B, S, H + 2 * num_kv_heads, D] with num_kv_heads = %d > 0, "
+                         "got %s" % (hkv, tuple(qkv.shape)))
+    if (qkv.size(2) - 2 * hkv) % hkv != 0:
+        raise ValueError("%d query heads do not split over %d key/value heads" % (
+            qkv.size(2) - 2 * hkv, hkv))
+    scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
+    kbias, klive = _key_mask(key_padding_mask, key_bias, qkv)
+    return AttentionFunction.apply(("gqa_qkv", hkv), causal, dropout_p, scale, _seed(dropout_p),
+                                   kbias, klive, None, qkv)
 
 
 def _varlen(cu_seqlens, max_seqlen, like, key_padding_mask, key_bias):
@@ -438,6 +496,7 @@ def fused_attention_varlen(q, k, v, cu_seqlens, max_seqlen=None, causal=False, d
     of the gradients that are not written are unspecified).
 
     Key masks are not combined with packing (ValueError)."""
+    _check_heads(q, k, "packed sequences (cu_seqlens)")
     cu_seqlens, max_seqlen = _varlen(cu_seqlens, max_seqlen, q, key_padding_mask, key_bias)
     scale = 1.0 / math.sqrt(q.size(-1)) if scale is None else scale
     return AttentionFunction.apply("varlen_qkv", causal, dropout_p, scale, _seed(dropout_p),

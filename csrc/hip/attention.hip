@@ -67,6 +67,16 @@
 // Fully masked queries and keys follow KMASK (o = 0, lse = -inf, dq = 0, dk = dv = 0; the
 // dQ kernel leaves the guarded lse and the refined D behind D).  The AMASK = false
 // instantiations are the kernels unchanged.
+//
+// Grouped-query heads (GQA kernels, VARLEN = AMASK = false): k and v are [B, Sk, Hkv, 64] with
+// Hkv = H / G, query head h reading key/value head h / G.  Forward and dQ keep their
+// workgroup per (query tile, b, query head) and only take K / V from head h / G; lse, D and
+// the dropout hash stay per query head.  A dK/dV workgroup belongs to (128 keys, b, key/value
+// head): it loads its K^T / V^T fragments once and walks the query tiles of all G query heads
+// of the group on one ring into one set of fp32 accumulators (see the kernel), so K / V are
+// read once per group, dK / dV are stored once, rounded once, and nothing is reduced
+// afterwards - no atomics, bitwise reproducible.  attention_gqa.hip compiles these
+// instantiations; the GQA = false ones are the kernels unchanged.
 #include "attention_common.h"
 
 namespace amd {
@@ -97,7 +107,7 @@ __global__ void __launch_bounds__(64) attn_kmask_prep_k(const M* __restrict__ ma
 }
 
 // ---------------------------------------------------------------------------- forward
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK, bool GQA>
 __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
@@ -114,6 +124,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
   int tile, bh;
   tile_of_block(CAUSAL, true, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
+  const int hk = GQA ? hh / a.G : hh;  // the key/value head this query head reads
   const int qb0 = tile * 128;
   [[maybe_unused]] int s0 = 0;
   if constexpr (VARLEN) {
@@ -126,8 +137,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
                                     (uint32_t)hl * kDropK
                               : 0u;
   const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
-  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh;
-  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh;
+  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hk * a.ksh;
+  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hk * a.vsh;
 
   // Q^T fragments (B operand of S^T = K . Q^T): d = 16s + 8hl + j
   v8 qf[4];
@@ -419,7 +430,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_fwd_k(AttnArgs a) {
 // make the compiler's vmcnt waits drain the prefetch).  KMASK: a lane's key bias is
 // loop-invariant (one load); a workgroup whose 128 keys are all dead writes zeros and
 // leaves, a wave whose 32 keys are all dead keeps the ring's barriers and skips the math.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK, bool GQA>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
@@ -435,7 +446,13 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   const int hl = lane >> 5, c32 = lane & 31;
   int tile, bh;
   tile_of_block(CAUSAL, false, tile, bh);
-  const int b = bh / a.H, hh = bh - b * a.H;
+  // GQA: the grid's rows are (b, key/value head).  hh is that head, the owner of K, V, dK and
+  // dV; bhq is the first of the a.G query heads that read it, whose Q / dO / lse / D rows and
+  // dropout hashes the loop below walks member by member.
+  const int nh = GQA ? a.H / a.G : a.H;
+  const int b = bh / nh, hh = bh - b * nh;
+  const int qh = GQA ? hh * a.G : hh;
+  const int bhq = GQA ? b * a.H + qh : bh;
   const int kb0 = tile * 128;
   [[maybe_unused]] int s0 = 0;
   if constexpr (VARLEN) {
@@ -467,15 +484,15 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     wave_dead = !__any(kbias > -INFINITY);
   }
   // dropout lattice point of (query key & 3, this lane's key quad)
-  const uint32_t kdrop = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)(key >> 2) * kDropK +
-                                    (uint32_t)(key & 3) * kDropQ
-                              : 0u;
-  const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
-  const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + hh * a.dsh;
+  uint32_t kdrop = DROP ? drop_base(a.seed, (uint32_t)bhq) + (uint32_t)(key >> 2) * kDropK +
+                              (uint32_t)(key & 3) * kDropQ
+                        : 0u;
+  const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + qh * a.qsh;
+  const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + qh * a.dsh;
   // KMASK / AMASK: the guarded copy of lse that the dQ kernel left behind D
   const float* lse = (KMASK || AMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
-                     (int64_t)bh * a.lse_stride;
-  const float* Dr = a.D + (int64_t)bh * a.lse_stride;
+                     (int64_t)bhq * a.lse_stride;
+  const float* Dr = a.D + (int64_t)bhq * a.lse_stride;
 
   // K^T / V^T fragments (B operands): key = this lane's column, d = 16s + 8hl + j
   v8 kf[4], vf[4];
@@ -552,13 +569,36 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
   PairTiles pt(AMASK ? a.ck + b * a.mks + (int64_t)tile * nqt : nullptr, nqt, lane);
   [[maybe_unused]] int nx = 0, slot = 0;
   [[maybe_unused]] bool full = false;
+  // GQA: the workgroup serves the a.G query heads of its key/value head one after the other,
+  // against the same K^T / V^T fragments and into the same accumulators: the flattened
+  // sequence of (member g, query tile qt), every member from its own qt0.  The ring runs
+  // through the head boundary: when a member's last tile is in hand its successor's first is
+  // prefetched, for which next_member() moves what issue() reads - wave-uniform bases, which
+  // stay in SGPRs - one head on; next_tile() then moves the math (g, the dropout lattice
+  // base, qt) when it gets there.
+  [[maybe_unused]] int g = 0;
+  [[maybe_unused]] auto next_member = [&]() {
+    Q += a.qsh;
+    dO += a.dsh;
+    lse += a.lse_stride;
+    Dr += a.lse_stride;
+  };
+  [[maybe_unused]] auto next_tile = [&](int qt) {
+    if (qt + 1 < nqt || g + 1 >= a.G) return qt + 1;
+    ++g;
+    // the lane's lattice point moves by the difference of the two heads' bases: scalar work
+    // and one add, no second per-lane term kept alive through the loop
+    if (DROP)
+      kdrop += drop_base(a.seed, (uint32_t)(bhq + g)) - drop_base(a.seed, (uint32_t)(bhq + g - 1));
+    return qt0;
+  };
   if constexpr (AMASK) {
     nx = pt.next();
     if (nx < nqt) issue(nx, 0);
   } else {
     if (qt0 < nqt) issue(qt0, 0);
   }
-  for (int qt = AMASK ? nx : qt0; qt < nqt; qt = AMASK ? nx : qt + 1) {
+  for (int qt = AMASK ? nx : qt0; qt < nqt; qt = AMASK ? nx : GQA ? next_tile(qt) : qt + 1) {
     if constexpr (AMASK) {
       full = pt.full;
       nx = pt.next();
@@ -567,11 +607,18 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     __syncthreads();
     if constexpr (AMASK) {
       if (nx < nqt) issue(nx, slot ^ 1);
+    } else if constexpr (GQA) {
+      if (qt + 1 < nqt) {
+        issue(qt + 1, slot ^ 1);
+      } else if (g + 1 < a.G) {
+        next_member();
+        issue(qt0, slot ^ 1);
+      }
     } else {
       if (qt + 1 < nqt) issue(qt + 1, (qt + 1 - qt0) & 1);
     }
-    const unsigned char* base = lds + (AMASK ? slot : ((qt - qt0) & 1)) * BUF;
-    if constexpr (AMASK) slot ^= 1;
+    const unsigned char* base = lds + (AMASK || GQA ? slot : ((qt - qt0) & 1)) * BUF;
+    if constexpr (AMASK || GQA) slot ^= 1;
     const unsigned char* Qr = base;
     const unsigned char* Qt = base + IMG;
     const unsigned char* Or = base + 2 * IMG;
@@ -662,8 +709,10 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
     // VGPRs, and the bias on top of that spilled (1-33 VGPRs, reloaded inside the loop)
     // in whichever instantiation the register allocator liked least.
     // AMASK: a full tile is clean, a mixed one masks both halves by its bits.
+    // GQA with DROP goes half by half too: the member walk's loop-carried state on top of the
+    // keep hashes put the straight-line block 1-4 VGPRs past the 256 (the compiler's report).
     const bool clean = AMASK ? full : (q0 + kAKT <= Sq) && (!CAUSAL || kw0 + 31 <= q0);
-    if (!KMASK && clean) {
+    if (!KMASK && !(GQA && DROP) && clean) {
       f32x16_t sc0, dp0, sc1, dp1;
       sdp(0, sc0, dp0);
       sdp(1, sc1, dp1);
@@ -702,7 +751,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dkdv_k(AttnBwdArgs a) {
 // K sits in LDS as a row image (A of S^T) and a transposed image (A of dQ^T);
 // V as a row image (A of dP^T = V . dO^T).  KMASK: the tile's bias rides the ring and
 // dead tiles are skipped as in the forward.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK, bool GQA>
 __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   // causal instantiations serve Sq == Sk only (the launchers refuse anything else) and
   // read the one length and stride, so they are the single-length kernels unchanged
@@ -719,6 +768,7 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   int tile, bh;
   tile_of_block(CAUSAL, true, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
+  const int hk = GQA ? hh / a.G : hh;  // the key/value head this query head reads
   const int qb0 = tile * 128;
   [[maybe_unused]] int s0 = 0;
   if constexpr (VARLEN) {
@@ -730,8 +780,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
   const uint32_t dbase = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)q * kDropQ +
                                     (uint32_t)hl * kDropK
                               : 0u;
-  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh;
-  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh;
+  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hk * a.ksh;
+  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hk * a.vsh;
 
   v8 qf[4], of[4];
   {
@@ -980,7 +1030,8 @@ __global__ void __launch_bounds__(kAT, 2) attn_bwd_dq_k(AttnBwdArgs a) {
 
 }  // namespace
 
-#ifndef ATTN_PAIRMASK_TU  // attention_pairmask.hip includes this file for the kernels alone
+#ifndef ATTN_KERNELS_ONLY  // attention_pairmask.hip and attention_gqa.hip include this file
+                           // for the kernels alone
 int attn_lse_stride(int S) { return (S + kAKT - 1) / kAKT * kAKT; }
 
 void attn_prepare_key_mask(const void* mask, AttnMaskKind kind, int B, int S, float* bias,
@@ -1009,6 +1060,7 @@ static bool head_dim_128(const char* who, int D) {
 }
 
 void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
+  if (p.Hkv != p.H) return attn_fwd_gqa(p, o, lse, st);
   if (head_dim_128("attn_fwd", p.D)) return attn_fwd_d128(p, o, lse, st);
   if (p.wq != nullptr) return attn_fwd_amask64(p, o, lse, st);
   AttnArgs a = kernel_args<AttnArgs>("attn_fwd", p);
@@ -1020,6 +1072,7 @@ void attn_fwd(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
 }
 
 void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
+  if (p.Hkv != p.H) return attn_bwd_gqa(p, g, st);
   if (head_dim_128("attn_bwd", p.D)) return attn_bwd_d128(p, g, st);
   if (p.wq != nullptr) return attn_bwd_amask64(p, g, st);
   AttnBwdArgs a = bwd_kernel_args("attn_bwd", p, g);
@@ -1032,6 +1085,7 @@ void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
 }
 #undef ATTN_KERNEL
 #undef ATTN_AMASK_KERNEL
-#endif  // ATTN_PAIRMASK_TU
+#undef ATTN_GQA_KERNEL
+#endif  // ATTN_KERNELS_ONLY
 
 }  // namespace amd

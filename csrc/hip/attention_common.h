@@ -212,6 +212,7 @@ struct AttnArgs {
   const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
   const int* cu;               // VARLEN: [B + 1] first token row of each sequence
   int T;                       // VARLEN: rows of the packed views
+  int G;                       // GQA: query heads per key/value head (H / Hkv), else 1
   // AMASK: the prepared pair mask (amd_kernels.h), batch strides in tiles (0 = shared)
   const unsigned long long* wq;
   const unsigned char* cq;
@@ -351,6 +352,7 @@ struct AttnBwdArgs {
   const unsigned char* klive;  // KMASK: [B][key_stride / 64] tile liveness
   const int* cu;               // VARLEN: [B + 1] first token row of each sequence
   int T;                       // VARLEN: rows of the packed views
+  int G;                       // GQA: query heads per key/value head (H / Hkv), else 1
   // AMASK: the prepared pair mask (amd_kernels.h), batch strides in tiles (0 = shared)
   const unsigned long long* wq;
   const unsigned char* cq;
@@ -394,6 +396,17 @@ static void require_pair_mask_alone(const char* who, const AttnProblem& p) {
     abort();
   }
 }
+static void require_heads(const char* who, const AttnProblem& p) {
+  if (p.Hkv <= 0 || p.H % p.Hkv != 0) {
+    fprintf(stderr, "%s: %d query heads do not split over %d key/value heads\n", who, p.H, p.Hkv);
+    abort();
+  }
+  if (p.Hkv != p.H && (p.cu_seqlens != nullptr || p.wq != nullptr)) {
+    fprintf(stderr, "%s: grouped-query heads (H = %d, Hkv = %d) take no cu_seqlens and no pair "
+                    "mask\n", who, p.H, p.Hkv);
+    abort();
+  }
+}
 static void require_causal_square(const char* who, bool causal, int Sq, int Sk) {
   if (causal && Sq != Sk) {
     fprintf(stderr, "%s: causal needs equal query and key lengths, got Sq = %d, Sk = %d\n", who,
@@ -412,6 +425,7 @@ A kernel_args(const char* who, const AttnProblem& p) {
   require_causal_square(who, p.causal, p.Sq, p.Sk);
   require_no_mask_when_packed(who, p);
   require_pair_mask_alone(who, p);
+  require_heads(who, p);
   A a{};
   a.q = p.q.p; a.qsb = p.q.sb; a.qss = p.q.ss; a.qsh = p.q.sh;
   a.k = p.k.p; a.ksb = p.k.sb; a.kss = p.k.ss; a.ksh = p.k.sh;
@@ -425,6 +439,7 @@ A kernel_args(const char* who, const AttnProblem& p) {
   a.seed = p.seed;
   a.kbias = p.kbias; a.klive = p.klive;
   a.cu = p.cu_seqlens; a.T = p.T;
+  a.G = p.H / p.Hkv;
   a.wq = p.wq; a.cq = p.cq; a.wk = p.wk; a.ck = p.ck;
   a.mqs = p.pm_sb;
   a.mks = p.pm_sb ? (int64_t)((p.Sk + 127) / 128) * ((p.Sq + kAKT - 1) / kAKT) : 0;
@@ -467,7 +482,7 @@ void dispatch(const AttnProblem& p, bool drop, F f) {
 // the kernel `name` instantiated for dispatch's (t, c, d, m, vl)
 #define ATTN_KERNEL(name)                                                                    \
   name<typename decltype(t)::type, decltype(c)::value, decltype(d)::value, decltype(m)::value, \
-       decltype(vl)::value, false>
+       decltype(vl)::value, false, false>
 
 // f(Elem<T>, drop): the 2 x 2 pair-mask (AMASK) instantiations, which exclude the other three
 template <typename F>
@@ -477,7 +492,24 @@ void dispatch_amask(const AttnProblem& p, bool drop, F f) {
   else flags(Elem<half_t>{});
 }
 #define ATTN_AMASK_KERNEL(name) \
-  name<typename decltype(t)::type, false, decltype(d)::value, false, false, true>
+  name<typename decltype(t)::type, false, decltype(d)::value, false, false, true, false>
+
+// f(Elem<T>, causal, drop, kmask): the 2 x 2 x 2 x 2 grouped-query (GQA) instantiations, which
+// exclude packed sequences and pair masks
+template <typename F>
+void dispatch_gqa(const AttnProblem& p, bool drop, F f) {
+  auto flag = [](bool on, auto g) { on ? g(std::true_type{}) : g(std::false_type{}); };
+  auto flags = [&](auto t) {
+    flag(p.causal, [&](auto c) {
+      flag(drop, [&](auto d) { flag(p.kbias != nullptr, [&](auto m) { f(t, c, d, m); }); });
+    });
+  };
+  if (p.dtype == DType::BF16) flags(Elem<bf16_t>{});
+  else flags(Elem<half_t>{});
+}
+#define ATTN_GQA_KERNEL(name)                                                                \
+  name<typename decltype(t)::type, decltype(c)::value, decltype(d)::value, decltype(m)::value, \
+       false, false, true>
 
 }  // namespace
 
@@ -487,5 +519,8 @@ void attn_bwd_d128(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 // the head dim 64 kernels under a pair mask (attention_pairmask.hip compiles them)
 void attn_fwd_amask64(const AttnProblem& p, void* o, float* lse, hipStream_t st);
 void attn_bwd_amask64(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
+// both head dims with fewer key/value heads than query heads (attention_gqa.hip compiles them)
+void attn_fwd_gqa(const AttnProblem& p, void* o, float* lse, hipStream_t st);
+void attn_bwd_gqa(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 
 }  // namespace amd

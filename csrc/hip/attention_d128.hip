@@ -51,6 +51,9 @@
 // buffered of the CU's 160 KiB.  The registers left over pay for the straight-line
 // two-half schedule of the mask-free instantiations (the key-mask ones go half by half,
 // as at D = 64: the compiler's report showed spills otherwise).
+//
+// Grouped-query heads (GQA = true, compiled by attention_gqa.hip): as in attention.hip - the
+// dK/dV workgroup belongs to a key/value head and walks its group's query heads on one ring.
 #include "attention_common.h"
 
 namespace amd {
@@ -117,7 +120,7 @@ __device__ __forceinline__ void settle(V (&f)[N]) {
 }
 
 // ---------------------------------------------------------------------------- forward
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK, bool GQA>
 __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
   int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
@@ -132,6 +135,7 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
   int tile, bh;
   tile_of_block(CAUSAL, true, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
+  const int hk = GQA ? hh / a.G : hh;  // the key/value head this query head reads
   const int qb0 = tile * 128;
   [[maybe_unused]] int s0 = 0;
   if constexpr (VARLEN) {
@@ -143,8 +147,8 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
                                     (uint32_t)hl * kDropK
                               : 0u;
   const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
-  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh;
-  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh;
+  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hk * a.ksh;
+  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hk * a.vsh;
 
   // Q^T fragments (B operand of S^T = K . Q^T): d = 16s + 8hl + j
   v8 qf[8];
@@ -420,7 +424,7 @@ __global__ void __launch_bounds__(kAT, 2) attn128_fwd_k(AttnArgs a) {
 // dK / dV: S[q][key] = Q . K^T unswapped with the wave's K^T / V^T fragments in registers,
 // dV^T = dO^T . P and dK^T = Q^T . dS from the accumulators (attention.hip); one workgroup
 // per CU, see the header for the register and LDS budget.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK, bool GQA>
 __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
   int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
@@ -433,7 +437,13 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
   const int hl = lane >> 5, c32 = lane & 31;
   int tile, bh;
   tile_of_block(CAUSAL, false, tile, bh);
-  const int b = bh / a.H, hh = bh - b * a.H;
+  // GQA: the grid's rows are (b, key/value head).  hh is that head, the owner of K, V, dK and
+  // dV; bhq is the first of the a.G query heads that read it, whose Q / dO / lse / D rows and
+  // dropout hashes the loop below walks member by member.
+  const int nh = GQA ? a.H / a.G : a.H;
+  const int b = bh / nh, hh = bh - b * nh;
+  const int qh = GQA ? hh * a.G : hh;
+  const int bhq = GQA ? b * a.H + qh : bh;
   const int kb0 = tile * 128;
   [[maybe_unused]] int s0 = 0;
   if constexpr (VARLEN) {
@@ -465,15 +475,15 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
     wave_dead = !__any(kbias > -INFINITY);
   }
   // dropout lattice point of (query key & 3, this lane's key quad)
-  const uint32_t kdrop = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)(key >> 2) * kDropK +
-                                    (uint32_t)(key & 3) * kDropQ
-                              : 0u;
-  const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + hh * a.qsh;
-  const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + hh * a.dsh;
+  uint32_t kdrop = DROP ? drop_base(a.seed, (uint32_t)bhq) + (uint32_t)(key >> 2) * kDropK +
+                              (uint32_t)(key & 3) * kDropQ
+                        : 0u;
+  const T* Q = static_cast<const T*>(a.q) + seq_off<VARLEN>(b, s0, a.qsb, a.qss) + qh * a.qsh;
+  const T* dO = static_cast<const T*>(a.dout) + seq_off<VARLEN>(b, s0, a.dsb, a.dss) + qh * a.dsh;
   // KMASK / AMASK: the guarded copy of lse that the dQ kernel left behind D
   const float* lse = (KMASK || AMASK ? a.D + (int64_t)a.B * a.H * a.lse_stride : a.lse) +
-                     (int64_t)bh * a.lse_stride;
-  const float* Dr = a.D + (int64_t)bh * a.lse_stride;
+                     (int64_t)bhq * a.lse_stride;
+  const float* Dr = a.D + (int64_t)bhq * a.lse_stride;
 
   // K^T / V^T fragments (B operands): key = this lane's column, d = 16s + 8hl + j
   v8 kf[8], vf[8];
@@ -573,6 +583,29 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
   PairTiles pt(AMASK ? a.ck + b * a.mks + (int64_t)tile * nqt : nullptr, nqt, lane);
   [[maybe_unused]] int nx = 0, slot = 0;
   [[maybe_unused]] bool full = false;
+  // GQA: the workgroup serves the a.G query heads of its key/value head one after the other,
+  // against the same K^T / V^T fragments and into the same accumulators: the flattened
+  // sequence of (member g, query tile qt), every member from its own qt0.  The ring runs
+  // through the head boundary: when a member's last tile is in hand its successor's first is
+  // prefetched, for which next_member() moves what issue() reads - wave-uniform bases, which
+  // stay in SGPRs - one head on; next_tile() then moves the math (g, the dropout lattice
+  // base, qt) when it gets there.
+  [[maybe_unused]] int g = 0;
+  [[maybe_unused]] auto next_member = [&]() {
+    Q += a.qsh;
+    dO += a.dsh;
+    lse += a.lse_stride;
+    Dr += a.lse_stride;
+  };
+  [[maybe_unused]] auto next_tile = [&](int qt) {
+    if (qt + 1 < nqt || g + 1 >= a.G) return qt + 1;
+    ++g;
+    // the lane's lattice point moves by the difference of the two heads' bases: scalar work
+    // and one add, no second per-lane term kept alive through the loop
+    if (DROP)
+      kdrop += drop_base(a.seed, (uint32_t)(bhq + g)) - drop_base(a.seed, (uint32_t)(bhq + g - 1));
+    return qt0;
+  };
   if constexpr (AMASK) {
     nx = pt.next();
     if (nx < nqt) issue(nx, 0);
@@ -581,7 +614,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
   }
   settle(kf);
   settle(vf);
-  for (int qt = AMASK ? nx : qt0; qt < nqt; qt = AMASK ? nx : qt + 1) {
+  for (int qt = AMASK ? nx : qt0; qt < nqt; qt = AMASK ? nx : GQA ? next_tile(qt) : qt + 1) {
     if constexpr (AMASK) {
       full = pt.full;
       nx = pt.next();
@@ -590,11 +623,18 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
     __syncthreads();
     if constexpr (AMASK) {
       if (nx < nqt) issue(nx, slot ^ 1);
+    } else if constexpr (GQA) {
+      if (qt + 1 < nqt) {
+        issue(qt + 1, slot ^ 1);
+      } else if (g + 1 < a.G) {
+        next_member();
+        issue(qt0, slot ^ 1);
+      }
     } else {
       if (qt + 1 < nqt) issue(qt + 1, (qt + 1 - qt0) & 1);
     }
-    const unsigned char* base = lds + (AMASK ? slot : ((qt - qt0) & 1)) * BUF;
-    if constexpr (AMASK) slot ^= 1;
+    const unsigned char* base = lds + (AMASK || GQA ? slot : ((qt - qt0) & 1)) * BUF;
+    if constexpr (AMASK || GQA) slot ^= 1;
     const unsigned char* Qr = base;
     const unsigned char* Qt = base + kTile;
     const unsigned char* Or = base + 2 * kTile;
@@ -717,7 +757,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dkdv_k(AttnBwdArgs a) {
 // (a lane's lse / D are scalars, dQ^T = K^T . dS^T from the accumulator); it also forms
 // D = rowsum(dO * O) and, under a key mask, leaves the guarded lse and the refined D for
 // the dK/dV kernel (attention.hip).  One workgroup per CU, see the header.
-template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK>
+template <typename T, bool CAUSAL, bool DROP, bool KMASK, bool VARLEN, bool AMASK, bool GQA>
 __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
   int Sq = a.Sq, Sk = CAUSAL ? a.Sq : a.Sk;
   [[maybe_unused]] const int kstride = CAUSAL ? a.lse_stride : a.key_stride;
@@ -731,6 +771,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
   int tile, bh;
   tile_of_block(CAUSAL, true, tile, bh);
   const int b = bh / a.H, hh = bh - b * a.H;
+  const int hk = GQA ? hh / a.G : hh;  // the key/value head this query head reads
   const int qb0 = tile * 128;
   [[maybe_unused]] int s0 = 0;
   if constexpr (VARLEN) {
@@ -742,8 +783,8 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
   const uint32_t dbase = DROP ? drop_base(a.seed, (uint32_t)bh) + (uint32_t)q * kDropQ +
                                     (uint32_t)hl * kDropK
                               : 0u;
-  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hh * a.ksh;
-  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hh * a.vsh;
+  const T* K = static_cast<const T*>(a.k) + seq_off<VARLEN>(b, s0, a.ksb, a.kss) + hk * a.ksh;
+  const T* V = static_cast<const T*>(a.v) + seq_off<VARLEN>(b, s0, a.vsb, a.vss) + hk * a.vsh;
 
   v8 qf[8], of[8];
   {
@@ -985,6 +1026,7 @@ __global__ void __launch_bounds__(kAT, 1) attn128_bwd_dq_k(AttnBwdArgs a) {
 
 }  // namespace
 
+#ifndef ATTN_KERNELS_ONLY  // attention_gqa.hip includes this file for the kernels alone
 void attn_fwd_d128(const AttnProblem& p, void* o, float* lse, hipStream_t st) {
   AttnArgs a = kernel_args<AttnArgs>("attn_fwd", p);
   a.o = o; a.lse = lse;
@@ -1018,5 +1060,7 @@ void attn_bwd_d128(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
 }
 #undef ATTN_KERNEL
 #undef ATTN_AMASK_KERNEL
+#undef ATTN_GQA_KERNEL
+#endif  // ATTN_KERNELS_ONLY
 
 }  // namespace amd

@@ -21,10 +21,10 @@
 //      the mask-free math, mixed ones test bits.
 //
 // The head dim 64 kernels are templates of attention.hip; this file includes it for them
-// (ATTN_PAIRMASK_TU leaves its host half out) so that their AMASK instantiations are
+// (ATTN_KERNELS_ONLY leaves its host half out) so that their AMASK instantiations are
 // compiled with this file's flags (tools/build_ext.py: packed fp32 VALU forms off, as for
 // attention_d128.hip) while attention.hip's own object, flags and code stay as they were.
-#define ATTN_PAIRMASK_TU 1
+#define ATTN_KERNELS_ONLY 1
 #include "attention.hip"
 
 namespace amd {
@@ -131,5 +131,6 @@ void attn_bwd_amask64(const AttnProblem& p, const AttnBwd& g, hipStream_t st) {
 }
 #undef ATTN_KERNEL
 #undef ATTN_AMASK_KERNEL
+#undef ATTN_GQA_KERNEL
 
 }  // namespace amd

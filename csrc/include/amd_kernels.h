@@ -506,9 +506,13 @@ struct AttnView {
 };
 // One attention problem, shared by the forward and the backward.
 struct AttnProblem {
-  AttnView q, k, v;  // q [B,Sq,H,D], k / v [B,Sk,H,D]
+  AttnView q, k, v;  // q [B,Sq,H,D], k / v [B,Sk,Hkv,D]
   int D = 64;        // head dim: 64 or 128 (attn_fwd / attn_bwd abort on anything else)
   int B, H;
+  // key/value heads: k / v (and dk / dv) are [B,Sk,Hkv,D], query head h reads key/value
+  // head h / (H / Hkv) (grouped-query attention; H % Hkv == 0, Hkv == H is plain multi-head).
+  // Hkv < H takes no cu_seqlens and no pair mask.
+  int Hkv;
   int Sq, Sk;        // query / key length, both > 0 at a launch
   float scale, dropout;
   uint32_t seed;
@@ -564,7 +568,7 @@ void attn_prepare_pair_mask(const unsigned char* mask, int64_t mask_sb, const un
 // then the dK/dV kernel (ceil(Sk/128) tiles).  No preprocess launch.
 struct AttnBwd {
   AttnView o, dout;      // inputs shaped like q
-  AttnView dq, dk, dv;   // strided outputs: dq like q, dk / dv like k
+  AttnView dq, dk, dv;   // strided outputs: dq like q, dk / dv like k (Hkv heads)
   const float* lse;      // [B][H][attn_lse_stride(Sq)]
   float* D;              // workspace shaped like lse, [2] of them with a key mask
 };

@@ -30,7 +30,8 @@ AttnView view_of(const at::Tensor& t, const char* what) {
   return {t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)};
 }
 
-// q [B, Sq, H, D], k / v [B, Sk, H, D]: one B, H, D and dtype, any strides
+// q [B, Sq, H, D], k / v [B, Sk, Hkv, D]: one B, D and dtype, any strides; Hkv divides H
+// (grouped-query heads: query head h reads key/value head h / (H / Hkv))
 AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                         bool causal, double dropout, int64_t seed, double scale) {
   AttnProblem L;
@@ -39,9 +40,12 @@ AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tens
   L.v = view_of(v, "v");
   TORCH_CHECK(v.sizes() == k.sizes(), "attn: k and v shapes differ: ", k.sizes(), " and ",
               v.sizes());
-  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3),
+  const int64_t H = q.size(2), Hkv = k.size(2);
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(3) == q.size(3) &&
+                  (Hkv == H || (Hkv > 0 && H % Hkv == 0)),
               "attn: q and k / v differ in batch or heads (or head dim): q ", q.sizes(), ", k ",
-              k.sizes(), " (only the sequence length may differ)");
+              k.sizes(), " (the sequence length may differ, and H = ", H,
+              " query heads may share Hkv = ", Hkv, " key/value heads where Hkv divides H)");
   TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type() &&
                   (q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf),
               "attn: bf16/fp16 q,k,v of one dtype");
@@ -51,8 +55,8 @@ AttnProblem make_launch(const at::Tensor& q, const at::Tensor& k, const at::Tens
               "attn: causal is defined for equal query and key lengths only, got Sq = ",
               q.size(1), ", Sk = ", k.size(1));
   TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "attn: dropout must be in [0, 1)");
-  L.B = (int)q.size(0); L.Sq = (int)q.size(1); L.Sk = (int)k.size(1); L.H = (int)q.size(2);
-  L.D = (int)q.size(3);
+  L.B = (int)q.size(0); L.Sq = (int)q.size(1); L.Sk = (int)k.size(1); L.H = (int)H;
+  L.Hkv = (int)Hkv; L.D = (int)q.size(3);
   L.scale = (float)scale; L.dropout = (float)dropout; L.seed = (uint32_t)seed;
   L.causal = causal; L.dtype = dtype_of(q);
   return L;
@@ -91,6 +95,8 @@ void check_key_mask(const c10::optional<at::Tensor>& bias, const c10::optional<a
 // (leading dim 1) or per batch element
 void check_pair_mask(const at::Tensor& wq, const at::Tensor& cq, const at::Tensor& wk,
                      const at::Tensor& ck, const at::Tensor& q, AttnProblem& L) {
+  TORCH_CHECK(L.Hkv == L.H, "attn: a pair mask is not combined with grouped-query heads (H = ",
+              L.H, ", Hkv = ", L.Hkv, ")");
   const int64_t nq128 = (L.Sq + 127) / 128, nq64 = (L.Sq + 63) / 64;
   const int64_t nk128 = (L.Sk + 127) / 128, nk64 = (L.Sk + 63) / 64;
   const int64_t Bm = cq.dim() == 3 ? cq.size(0) : -1;
@@ -158,7 +164,7 @@ AttnProblem make_varlen_launch(const at::Tensor& q, const at::Tensor& k, const a
               "attn varlen: max_seqlen must be in (0, 2^24), got ", max_seqlen);
   TORCH_CHECK(q.size(0) < (int64_t{1} << 31), "attn varlen: too many tokens: ", q.size(0));
   TORCH_CHECK(dropout >= 0.0 && dropout < 1.0, "attn: dropout must be in [0, 1)");
-  L.B = (int)cu.size(0) - 1; L.H = (int)q.size(1); L.D = (int)q.size(2);
+  L.B = (int)cu.size(0) - 1; L.H = L.Hkv = (int)q.size(1); L.D = (int)q.size(2);
   TORCH_CHECK((int64_t)L.B * L.H <= 65535, "attn varlen: sequences x heads = ",
               (int64_t)L.B * L.H, " exceeds the 65535 rows of a launch grid");
   L.Sq = L.Sk = (int)max_seqlen;

@@ -8,6 +8,7 @@
     python tools/microbench.py lamb    # FusedLAMB / FusedAdam on BERT-large's 336M params
     python tools/microbench.py attn-packed  # packed (cu_seqlens) vs padded + key mask attention
     python tools/microbench.py attn-pairmask  # boolean [S, S] masks vs SDPA and the causal kernels
+    python tools/microbench.py attn-gqa  # grouped-query heads vs expanded k / v, SDPA, equal heads
 """
 from __future__ import annotations
 
@@ -555,6 +556,7 @@ def bench_attn(args):
     bench_attn_packed(args)
     bench_attn_d128(args)
     bench_attn_pairmask(args)
+    bench_attn_gqa(args)
 
 
 def bench_attn_pairmask(args):
@@ -694,6 +696,69 @@ def bench_attn_d128(args):
                 name, n, med([tf_ for tf_, _ in times[n]]), med([tb for _, tb in times[n]]),
                 med(tot), 100 * (max(tot) - min(tot)) / med(tot), fl / (med(tot) * 1e-6) / 1e12),
                 flush=True)
+
+
+def bench_attn_gqa(args):
+    """Grouped-query heads (csrc/hip/attention_gqa.hip): bf16 causal forward + backward through
+    the public op with k / v of Hkv heads, against (a) what users paid before - the same op
+    on k / v expanded with repeat_interleave, the expansion and autograd's group sum included -
+    (b) SDPA with enable_gqa=True and (c) the equal-head call (k / v of H heads), the floor.
+    The variants alternate in one process over ROUNDS rounds; prints each one's median and
+    spread, (max - min) / median.  The dK/dV grid is B * Hkv * ceil(S / 128) workgroups."""
+    from apex_example_amd.ops import fused_attention
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    print("| shape (B x H x S, D, Hkv) | dK/dV workgroups | variant | fwd + bwd us | spread | vs expanded |")
+    print("|---|---|---|---|---|---|")
+    for b, h, s_, d, hkv in [(8, 16, 1024, 64, 4), (8, 16, 1024, 64, 1), (4, 16, 2048, 128, 2),
+                             (4, 16, 2048, 128, 1), (1, 16, 2048, 128, 1)]:
+        g = h // hkv
+        q, do = (torch.randn(b, s_, h, d, device=dev, dtype=dt) for _ in range(2))
+        q.requires_grad_(True)
+        k, v = (torch.randn(b, s_, hkv, d, device=dev, dtype=dt, requires_grad=True)
+                for _ in range(2))
+        kf, vf = (torch.randn(b, s_, h, d, device=dev, dtype=dt, requires_grad=True)
+                  for _ in range(2))
+        sq, sk, sv = (t.detach().transpose(1, 2).contiguous().requires_grad_(True)
+                      for t in (q, k, v))
+        sdo = do.transpose(1, 2).contiguous()
+
+        def grouped():
+            torch.autograd.grad(fused_attention(q, k, v, causal=True), (q, k, v), do)
+
+        def expanded():
+            kx, vx = (t.repeat_interleave(g, dim=2) for t in (k, v))
+            torch.autograd.grad(fused_attention(q, kx, vx, causal=True), (q, k, v), do)
+
+        def sdpa():
+            o = F.scaled_dot_product_attention(sq, sk, sv, is_causal=True, enable_gqa=True)
+            torch.autograd.grad(o, (sq, sk, sv), sdo)
+
+        def floor():
+            torch.autograd.grad(fused_attention(q, kf, vf, causal=True), (q, kf, vf), do)
+
+        variants = [("gqa kernels", grouped), ("expanded k / v (before)", expanded),
+                    ("sdpa enable_gqa", sdpa), ("equal heads (floor)", floor)]
+        t_end = time.time() + 2.0  # clock / first-use ramp, as in bench_attn
+        while time.time() < t_end:
+            grouped()
+            torch.cuda.synchronize()
+        times = {n: [] for n, _ in variants}
+        for _ in range(ROUNDS):
+            for n, fn in variants:
+                try:
+                    times[n].append(timeit(fn, iters=20, warmup=5))
+                except Exception as e:  # noqa: BLE001
+                    print("%s failed: %s" % (n, str(e)[:200]))
+        med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+        base = med(times["expanded k / v (before)"])
+        for n, _ in variants:
+            if len(times[n]) < ROUNDS:
+                continue
+            t = times[n]
+            print("| %d x %d x %d, %d, %d | %d | %s | %.0f | %.1f %% | %.2f x |" % (
+                b, h, s_, d, hkv, b * hkv * ((s_ + 127) // 128), n, med(t),
+                100 * (max(t) - min(t)) / med(t), med(t) / base), flush=True)
 
 
 def bench_attn_packed(args):
@@ -1010,13 +1075,13 @@ def bench_conv1x1_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
-                             "attn", "attn-packed", "attn-d128", "attn-pairmask"])
+                             "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
      "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn,
      "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128,
-     "attn-pairmask": bench_attn_pairmask}[a.what](a)
+     "attn-pairmask": bench_attn_pairmask, "attn-gqa": bench_attn_gqa}[a.what](a)
 
 
 if __name__ == "__main__":
