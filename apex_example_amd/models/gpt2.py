@@ -1,7 +1,9 @@
 """GPT-2 (Radford et al. 2019) language model defined in-repo: pre-LN decoder
 blocks with FusedLayerNorm, causal attention on the gfx950 fused attention
 kernels (ops/attention.py; PyTorch SDPA off-GPU / fp32),
-tanh-GELU MLP and an LM head tied to the token embedding.
+tanh-GELU MLP and an LM head tied to the token embedding.  ``generate`` samples with a
+``KVCache``: the prompt runs through the causal kernels once, every further token through the
+split-KV decode kernels (``fused_attention_decode``).
 
 gpt2_medium(): 24 layers, d_model 1024, 16 heads, vocab 50257, 1024 positions
 = 354,823,168 parameters in 292 tensors.
@@ -50,6 +52,36 @@ def _ln(cfg, n):
     return nn.LayerNorm(n, eps=cfg.layer_norm_epsilon)
 
 
+class KVCache:
+    """Keys and values of the tokens a model has seen, for ``GPT2LMHeadModel.forward(...,
+    cache=)``: per layer one packed [B, max_len, 2, Hkv, D] buffer (allocated at the layer's
+    first use, in its activations' dtype), one int32 [B] length tensor on the device, which the
+    decode kernels read, and the same length as a host integer, so that choosing between the
+    prefill and the decode path costs no sync.  One length per batch: ragged prompts are not
+    served."""
+
+    def __init__(self, batch, max_len):
+        self.batch, self.max_len = int(batch), int(max_len)
+        self.kv = {}         # layer -> [B, max_len, 2, Hkv, D]
+        self.lengths = None  # int32 [B], on the device of the first layer's buffer
+        self.length = 0
+
+    def layer(self, idx, like):
+        """The buffer of layer ``idx`` for keys shaped and typed like ``like`` [B, s, Hkv, D]."""
+        if idx not in self.kv:
+            self.kv[idx] = like.new_empty(self.batch, self.max_len, 2, like.size(2), like.size(3))
+            if self.lengths is None:
+                self.lengths = torch.full((self.batch,), self.length, dtype=torch.int32,
+                                          device=like.device)
+        return self.kv[idx]
+
+    def advance(self, n):
+        """After every layer has stored ``n`` new tokens."""
+        self.length += n
+        if self.lengths is not None:
+            self.lengths += n
+
+
 class GPT2Attention(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -66,13 +98,16 @@ class GPT2Attention(nn.Module):
         self.resid_dropout = nn.Dropout(cfg.resid_pdrop)
         self.fused = cfg.fused_attention
         self.fused_dense = cfg.fused_dense
+        self.layer_idx = 0  # its slot in a KVCache; GPT2LMHeadModel numbers its blocks
 
     def _lin(self, m, x):
         return fused_dense_function(x, m.weight, m.bias) if self.fused_dense else m(x)
 
-    def forward(self, x, resid_dropout=True):
+    def forward(self, x, resid_dropout=True, cache=None):
         b, s, e = x.shape
         drop = self.resid_dropout if resid_dropout else (lambda t: t)
+        if cache is not None:
+            return drop(self._lin(self.c_proj, self._cached(x, cache)))
         if self.hkv is not None:
             return drop(self._lin(self.c_proj, self._grouped(x)))
         qkv = self._lin(self.c_attn, x).view(b, s, 3, self.h, self.d)
@@ -85,6 +120,37 @@ class GPT2Attention(nn.Module):
         o = o.transpose(1, 2).reshape(b, s, e)
         return drop(self._lin(self.c_proj, o))
 
+    def _cached(self, x, cache):
+        """Attention output [b, s, e] of s new tokens behind the ``cache.length`` tokens of a
+        ``KVCache``, storing their keys and values (the model advances the lengths).  An empty
+        cache is a prefill on the causal kernels; a filled one a decode step, which appends in
+        its own launch.  Off the GPU / in fp32: SDPA over the filled rows."""
+        b, s, e = x.shape
+        h, hkv, d = self.h, self.hkv or self.h, self.d
+        y = self._lin(self.c_attn, x)
+        if self.hkv is None:
+            q, k, v = y.view(b, s, 3, h, d).unbind(2)
+        else:
+            q, k, v = y.view(b, s, h + 2 * hkv, d).split((h, hkv, hkv), 2)
+        L = cache.length
+        if b != cache.batch or L + s > cache.max_len:
+            raise ValueError("the KV cache holds %d x %d tokens: no room for batch %d, %d + %d "
+                             "tokens" % (cache.batch, cache.max_len, b, L, s))
+        kv = cache.layer(self.layer_idx, k)
+        fused = self.fused and fused_attn.supported(q, d)
+        if fused and L > 0:
+            return fused_attn.fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], cache.lengths,
+                                                     k_new=k, v_new=v).view(b, s, e)
+        kv[:, L:L + s, 0] = k
+        kv[:, L:L + s, 1] = v
+        if fused:
+            return fused_attn.fused_attention(q, k, v, causal=True).view(b, s, e)
+        g = h // hkv
+        kk, vv = (kv[:, :L + s, i].transpose(1, 2).repeat_interleave(g, 1) for i in (0, 1))
+        # bottom-right causal mask: new token i sees keys j <= L + i
+        keep = torch.ones(s, L + s, dtype=torch.bool, device=x.device).tril(L)
+        o = F.scaled_dot_product_attention(q.transpose(1, 2), kk, vv, attn_mask=keep)
+        return o.transpose(1, 2).reshape(b, s, e)
 
     def _grouped(self, x):
         """Attention output [b, s, e] with n_kv_head key/value heads."""
@@ -126,18 +192,19 @@ class GPT2Block(nn.Module):
         self.ln_2 = _ln(cfg, cfg.n_embd)
         self.mlp = GPT2MLP(cfg)
 
-    def forward(self, x):
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x, cache=None):
+        x = x + self.attn(self.ln_1(x), cache=cache)
         return x + self.mlp(self.ln_2(x))
 
-    def forward_joined(self, x, y, next_ln):
+    def forward_joined(self, x, y, next_ln, cache=None):
         """Same block with the sublayer joins fused: ``y`` = ln_1(x) is given,
         returns (next_ln(x'), x') for the block output x'.  Each join (dropout,
         residual add, the following LayerNorm) is one kernel each way."""
         # y only feeds autocast GEMMs (c_attn / c_fc / the tied LM head): under O1 it
         # leaves the join in the GEMM dtype instead of fp32 + a cast kernel
         y16 = torch.is_autocast_enabled("cuda")
-        y, x = fused_add_dropout_layer_norm(x, self.attn(y, resid_dropout=False), self.ln_2,
+        y, x = fused_add_dropout_layer_norm(x, self.attn(y, resid_dropout=False, cache=cache),
+                                            self.ln_2,
                                             self.attn.resid_dropout.p, self.training, y16)
         return fused_add_dropout_layer_norm(x, self.mlp(y, dropout=False), next_ln,
                                             self.mlp.dropout.p, self.training, y16)
@@ -152,6 +219,8 @@ class GPT2LMHeadModel(nn.Module):
         self.drop = nn.Dropout(cfg.embd_pdrop)
         self.h = nn.ModuleList([GPT2Block(cfg) for _ in range(cfg.n_layer)])
         self.ln_f = _ln(cfg, cfg.n_embd)
+        for i, block in enumerate(self.h):
+            block.attn.layer_idx = i
         self.apply(self._init)
         # GPT-2: scale the residual projections by 1/sqrt(2 * n_layer)
         for name, p in self.named_parameters():
@@ -166,9 +235,16 @@ class GPT2LMHeadModel(nn.Module):
         elif isinstance(m, nn.Embedding):
             nn.init.normal_(m.weight, std=self.config.initializer_range)
 
-    def forward(self, input_ids):
+    def forward(self, input_ids, cache=None):
+        """Logits [B, S, vocab].  With a ``KVCache``, ``input_ids`` are the tokens that follow
+        the ``cache.length`` ones it holds: their keys and values are stored, their positions
+        start at that length and they attend to everything before them (inference only)."""
         s = input_ids.size(1)
-        pos = torch.arange(s, device=input_ids.device).unsqueeze(0)
+        p0 = 0 if cache is None else cache.length
+        if cache is not None and p0 + s > self.config.n_positions:
+            raise ValueError("%d + %d tokens exceed n_positions = %d" % (
+                p0, s, self.config.n_positions))
+        pos = torch.arange(p0, p0 + s, device=input_ids.device).unsqueeze(0)
         x = self.drop(self.wte(input_ids) + self.wpe(pos))
         if self.config.fused_dense and x.is_cuda and torch.is_autocast_enabled("cuda"):
             # O1: every dense weight / bias cast to the GEMM dtype in one launch
@@ -176,20 +252,47 @@ class GPT2LMHeadModel(nn.Module):
                                                    blk.mlp.c_fc, blk.mlp.c_proj)
                      for p in (m.weight, m.bias)]
             with cast_params_once(dense, torch.get_autocast_dtype("cuda")):
-                return self._blocks(x)
-        return self._blocks(x)
+                return self._blocks(x, cache)
+        return self._blocks(x, cache)
 
-    def _blocks(self, x):
+    def _blocks(self, x, cache=None):
         if self.config.fused_residual_ln:
             y = self.h[0].ln_1(x)
             for i, block in enumerate(self.h):
                 nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
-                y, x = block.forward_joined(x, y, nxt)
-            return F.linear(y, self.wte.weight)  # tied LM head
-        for block in self.h:
-            x = block(x)
-        x = self.ln_f(x)
-        return F.linear(x, self.wte.weight)  # tied LM head
+                y, x = block.forward_joined(x, y, nxt, cache)
+        else:
+            for block in self.h:
+                x = block(x, cache)
+            y = self.ln_f(x)
+        if cache is not None:
+            cache.advance(x.size(1))
+        return F.linear(y, self.wte.weight)  # tied LM head
+
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens, temperature=0.0):
+        """input_ids [B, S0] (one prompt length per batch) -> [B, S0 + max_new_tokens]: greedy
+        at temperature 0, else sampled from softmax(logits / temperature).  Runs in eval mode
+        with a ``KVCache``: one forward over the prompt, then one token per step."""
+        b, s0 = input_ids.shape
+        if s0 + max_new_tokens > self.config.n_positions:
+            raise ValueError("%d prompt + %d new tokens exceed n_positions = %d" % (
+                s0, max_new_tokens, self.config.n_positions))
+        training = self.training
+        self.eval()
+        try:
+            cache = KVCache(b, s0 + max_new_tokens)
+            out, step = input_ids, input_ids
+            for n in range(max_new_tokens):
+                logits = self(step, cache=cache)[:, -1].float()
+                if temperature > 0.0:
+                    step = torch.multinomial(torch.softmax(logits / temperature, -1), 1)
+                else:
+                    step = logits.argmax(-1, keepdim=True)
+                out = torch.cat([out, step], 1)
+            return out
+        finally:
+            self.train(training)
 
 
 def lm_loss(logits, input_ids, fused=True):

@@ -59,12 +59,28 @@ that layout.  The dropout mask is that of the same call on K / V expanded to H h
 combined with ``attn_mask`` or packed sequences (ValueError).  docs/PERF.md, "Attention:
 grouped-query heads".
 
+Decode over a KV cache: ``fused_attention_decode(q, k_cache, v_cache, cache_seqlens)`` attends
+the Sq newest tokens q [B, Sq, H, D] (Sq of 1 to a few) to the keys of [B, Smax, Hkv, D] cache
+views (any strides: the halves of one packed [B, Smax, 2, Hkv, D] buffer), of which
+``cache_seqlens`` (int32 [B] on the GPU, read by the kernels only: no host sync, graph-capture
+safe, a captured graph may be replayed after ``cache_seqlens += Sq``) says how many rows are
+filled.  With ``k_new`` / ``v_new`` the new rows are first appended behind them.  The mask is
+causal and aligned bottom-right (query i sees keys j <= L_b - Sq + i), rows at or past L_b are
+never read, a query that sees no key gets o = 0 and lse = -inf.  Forward only: no dropout,
+no key or pair mask, no gradient.  Its kernels (csrc/hip/attention_decode.hip) are not the
+training forward: the G query heads of a group times the Sq tokens fill one MFMA tile so K / V
+are read once per group, the four waves of a workgroup and ``num_splits`` workgroups split
+the keys, and a second launch joins the splits in a fixed order (bitwise reproducible for a
+given ``num_splits``).  docs/PERF.md, "Attention: decode over a KV cache".
+
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size (the query and key lengths may differ) and H query heads over Hkv key/value heads
 with H % Hkv == 0 (Hkv < H neither with a pair mask nor packed), no mask other than
 a per-batch key mask, a boolean pair mask (an additive [Tq, Tk] ``attn_mask`` is not
 fused) or, at equal lengths, the causal mask; packed sequences ([T, H, D] with ``cu_seqlens``): q, k and v of one token
-and head count, self-attention per sequence, optional causal mask, no key mask.  Callers
+and head count, self-attention per sequence, optional causal mask, no key mask.  A decode
+step over a KV cache (``fused_attention_decode``) takes the same dtypes, head dims and head
+groupings, forward only.  Callers
 fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
 from __future__ import annotations
@@ -514,3 +530,65 @@ def fused_attention_varlen_qkv(qkv, cu_seqlens, max_seqlen=None, causal=False, d
     scale = 1.0 / math.sqrt(qkv.size(-1)) if scale is None else scale
     return AttentionFunction.apply("varlen_packed_qkv", causal, dropout_p, scale,
                                    _seed(dropout_p), None, None, (cu_seqlens, max_seqlen), qkv)
+
+
+def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None,
+                           scale=None, num_splits=None, return_lse=False):
+    """One decode step over a KV cache.  q: [B, Sq, H, D], the Sq newest tokens; k_cache,
+    v_cache: [B, Smax, Hkv, D] views (any batch / sequence / head strides; H % Hkv == 0, D = 64
+    or 128, bf16 / fp16); cache_seqlens: int32 [B] on the GPU, the keys already in the cache,
+    read by the kernels only (no host sync).  With k_new and v_new [B, Sq, Hkv, D] the rows are
+    first written into the caches at rows cache_seqlens[b] .. cache_seqlens[b] + Sq - 1 and the
+    visible length is L_b = cache_seqlens[b] + Sq, else L_b = cache_seqlens[b]; L_b is clipped
+    to Smax on the device and no row outside the views is read or written.  Query i sees keys
+    j <= L_b - Sq + i; a query that sees no key gets o = 0 and lse = -inf.  cache_seqlens is not
+    advanced: the caller adds Sq (on the device) after the call.
+
+    num_splits: workgroups that split each cache (None: chosen from the shapes and the device's
+    CU count, never from the lengths); results are bitwise reproducible for a given value.
+    -> o [B, Sq, H, D] contiguous and, with return_lse, the fp32 [B, H, Sq] lse in log2 units.
+    Forward only: ValueError if a gradient is asked of it."""
+    named = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)]
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new come as a pair")
+    if k_new is not None:
+        named += [("k_new", k_new), ("v_new", v_new)]
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError("%s must be a 4-d tensor, got %s" % (
+                name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU, got a %s tensor" % (name, t.device))
+        if t.device != q.device or t.dtype != q.dtype:
+            raise ValueError("%s is %s on %s, q %s on %s" % (name, t.dtype, t.device, q.dtype,
+                                                            q.device))
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("decode takes bf16 / fp16 tensors, got %s" % q.dtype)
+    B, Sq, H, D = q.shape
+    if D not in HEAD_DIMS:
+        raise ValueError("head dim must be one of %s, got %d" % (HEAD_DIMS, D))
+    if k_cache.shape != v_cache.shape or k_cache.size(0) != B or k_cache.size(3) != D:
+        raise ValueError("k_cache and v_cache must be [B, Smax, Hkv, D] with B = %d, D = %d, got "
+                         "%s and %s" % (B, D, tuple(k_cache.shape), tuple(v_cache.shape)))
+    _check_heads(q, k_cache)
+    Hkv = k_cache.size(2)
+    if k_new is not None and not (tuple(k_new.shape) == tuple(v_new.shape) == (B, Sq, Hkv, D)):
+        raise ValueError("k_new and v_new must be [B, Sq, Hkv, D] = [%d, %d, %d, %d], got %s and "
+                         "%s" % (B, Sq, Hkv, D, tuple(k_new.shape), tuple(v_new.shape)))
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or \
+            tuple(cache_seqlens.shape) != (B,):
+        raise ValueError("cache_seqlens must be an int32 [B] = [%d] tensor" % B)
+    if cache_seqlens.device != q.device:
+        raise ValueError("cache_seqlens is on %s, q on %s" % (cache_seqlens.device, q.device))
+    if not cache_seqlens.is_contiguous():
+        raise ValueError("cache_seqlens must be contiguous: the kernels read the tensor itself")
+    if torch.is_grad_enabled() and any(t.requires_grad for _, t in named):
+        raise ValueError("fused_attention_decode is forward only: call it under torch.no_grad() "
+                         "or on detached tensors")
+    cap = _C().DECODE_MAX_SPLITS
+    if num_splits is not None and not 1 <= int(num_splits) <= cap:
+        raise ValueError("num_splits must be in [1, %d], got %s" % (cap, num_splits))
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    o, lse = _C().decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, float(scale),
+                         0 if num_splits is None else int(num_splits))
+    return (o, lse) if return_lse else o

@@ -574,6 +574,34 @@ struct AttnBwd {
 };
 void attn_bwd(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 
+// Decode step over a KV cache (attention_decode.hip; forward only): q [B,Sq,H,D], the Sq
+// newest tokens, against the caches k / v [B,Smax,Hkv,D] (any strides).  cache_seqlens [B]
+// (int32, device) holds the keys in the cache before the call and is read by the kernels
+// only.  With k_new / v_new [B,Sq,Hkv,D] (both or neither; p == nullptr = none) the rows are
+// first copied to cache rows cache_seqlens[b] + i and the visible length is L_b =
+// cache_seqlens[b] + Sq, else cache_seqlens[b]; L_b is clipped to Smax on the device.  The
+// mask is causal, aligned bottom-right (query i sees keys j <= L_b - Sq + i); a query that
+// sees no key gets o = 0, lse = -inf.  The keys are split over nsplit workgroups per (b,
+// key/value head, 32 rows); nsplit > 1 needs the fp32 workspace o_part [nsplit][B][Sq][H][D]
+// and lse_part [nsplit][B][H][Sq], joined in split order by a second launch (no atomics).
+constexpr int kAttnDecodeMaxSplits = 64;
+struct AttnDecode {
+  AttnView q, k, v, k_new, v_new;
+  const int32_t* cache_seqlens = nullptr;
+  int D = 64, B = 0, H = 0, Hkv = 0, Sq = 0, Smax = 0;
+  float scale = 1.f;
+  DType dtype;  // BF16 or F16
+  int nsplit = 1;
+  float* o_part = nullptr;
+  float* lse_part = nullptr;
+};
+// the split count for a problem's shapes on a device of num_cus compute units (never from the
+// lengths): about two workgroups per CU, at least four 64-key tiles of Smax per split, at
+// most kAttnDecodeMaxSplits; R = (H / Hkv) * Sq rows per key/value head
+int attn_decode_splits(int B, int Hkv, int R, int Smax, int num_cus);
+// o [B][Sq][H][D] contiguous, lse [B][H][Sq] (log2 units)
+void attn_decode(const AttnDecode& p, void* o, float* lse, hipStream_t st);
+
 // ---- fused softmax cross entropy with label smoothing (xentropy.hip) ---------
 // x [rows, V] row-major (T = fp32/fp16/bf16); loss [rows] (TO), lse [rows] fp32
 void xentropy_fwd(const void* x, DType tx, const int64_t* labels, int64_t rows, int V,

@@ -418,4 +418,76 @@ void attn_bwd_varlen_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor 
   attn_bwd(F, G, cur_stream());
 }
 
+std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cache,
+                                                  at::Tensor v_cache, at::Tensor cache_seqlens,
+                                                  c10::optional<at::Tensor> k_new,
+                                                  c10::optional<at::Tensor> v_new, double scale,
+                                                  int64_t num_splits) {
+  c10::NoGradGuard no_grad_;
+  AttnDecode P;
+  P.q = view_of(q, "q");
+  P.k = view_of(k_cache, "k_cache");
+  P.v = view_of(v_cache, "v_cache");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "attn decode: k_cache and v_cache shapes "
+              "differ: ", k_cache.sizes(), " and ", v_cache.sizes());
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  const int64_t Smax = k_cache.size(1), Hkv = k_cache.size(2);
+  TORCH_CHECK(k_cache.size(0) == B && k_cache.size(3) == D && Hkv > 0 && H % Hkv == 0,
+              "attn decode: q and the caches differ in batch or head dim, or the heads do not "
+              "split: q ", q.sizes(), ", k_cache ", k_cache.sizes());
+  auto same = [&](const at::Tensor& t) {
+    return t.scalar_type() == q.scalar_type() && t.device() == q.device();
+  };
+  TORCH_CHECK((q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf) &&
+                  same(k_cache) && same(v_cache),
+              "attn decode: bf16/fp16 q and caches of one dtype on one device");
+  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == q.device() &&
+                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
+                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
+              "attn decode: cache_seqlens must be a contiguous int32 [B] tensor on q's device, "
+              "got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
+  TORCH_CHECK(k_new.has_value() == v_new.has_value(),
+              "attn decode: k_new and v_new come as a pair");
+  if (k_new.has_value()) {
+    P.k_new = view_of(*k_new, "k_new");
+    P.v_new = view_of(*v_new, "v_new");
+    const std::vector<int64_t> dims{B, Sq, Hkv, D};
+    const at::IntArrayRef want(dims);
+    TORCH_CHECK(k_new->sizes() == want && v_new->sizes() == want && same(*k_new) && same(*v_new),
+                "attn decode: k_new and v_new must be [B, Sq, Hkv, D] = ", want,
+                " of q's dtype and device, got ", k_new->sizes(), " and ", v_new->sizes());
+  }
+  TORCH_CHECK(Smax < (int64_t{1} << 24) && Sq < (int64_t{1} << 24),
+              "attn decode: Smax and Sq must be below 2^24");
+  const int64_t R = H / Hkv * Sq;
+  TORCH_CHECK(B * Hkv <= 65535 && (R + 31) / 32 <= 65535,
+              "attn decode: batch x key/value heads = ", B * Hkv, " or rows per group = ", R,
+              " exceeds a launch grid");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= kAttnDecodeMaxSplits,
+              "attn decode: num_splits must be in [1, ", kAttnDecodeMaxSplits, "], got ",
+              num_splits);
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
+  P.scale = (float)scale;
+  P.dtype = dtype_of(q);
+  at::Tensor o = at::empty({B, Sq, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (B == 0 || Sq == 0) return {o, lse};
+  int cus = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                    q.get_device()) == hipSuccess,
+              "attn decode: cannot read the device's CU count");
+  P.nsplit = num_splits > 0 ? (int)num_splits
+                            : attn_decode_splits(P.B, P.Hkv, (int)R, P.Smax, cus);
+  at::Tensor o_part, lse_part;
+  if (P.nsplit > 1) {
+    o_part = at::empty({P.nsplit, B, Sq, H, D}, q.options().dtype(at::kFloat));
+    lse_part = at::empty({P.nsplit, B, H, Sq}, q.options().dtype(at::kFloat));
+    P.o_part = o_part.data_ptr<float>();
+    P.lse_part = lse_part.data_ptr<float>();
+  }
+  attn_decode(P, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
 }  // namespace amd

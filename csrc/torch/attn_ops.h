@@ -78,4 +78,19 @@ void attn_bwd_varlen_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor 
                         double dropout, int64_t seed, double scale, at::Tensor dq, at::Tensor dk,
                         at::Tensor dv);
 
+// Decode step over a KV cache (csrc/hip/attention_decode.hip; forward only, no gradient).
+// q: [B, Sq, H, D], the Sq newest tokens; k_cache, v_cache: [B, Smax, Hkv, D] views (any
+// batch / sequence / head strides, head dim contiguous, 16-B aligned rows; H % Hkv == 0, D =
+// 64 or 128, one bf16 / fp16 dtype); cache_seqlens: contiguous int32 [B] on q's device, the
+// keys in the cache before the call, read by the kernels only (no host sync).  k_new / v_new
+// [B, Sq, Hkv, D] (both or neither) are first written to cache rows cache_seqlens[b] + i.
+// num_splits: 0 = chosen from the shapes and the device's CU count, else 1 ..
+// kAttnDecodeMaxSplits.  Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2 units).
+// B == 0 or Sq == 0 launches nothing.
+std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cache,
+                                                  at::Tensor v_cache, at::Tensor cache_seqlens,
+                                                  c10::optional<at::Tensor> k_new,
+                                                  c10::optional<at::Tensor> v_new, double scale,
+                                                  int64_t num_splits);
+
 }  // namespace amd

@@ -125,6 +125,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_seqlens"),
            py::arg("max_seqlen"), py::arg("causal"), py::arg("dropout"), py::arg("seed"),
            py::arg("scale"), py::arg("dq"), py::arg("dk"), py::arg("dv"));
+  attn.def("decode", &attn_decode_op, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+           py::arg("cache_seqlens"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(),
+           py::arg("scale") = 1.0, py::arg("num_splits") = 0);
+  attn.attr("DECODE_MAX_SPLITS") = kAttnDecodeMaxSplits;
+  attn.def("decode_splits", &attn_decode_splits, py::arg("B"), py::arg("Hkv"), py::arg("R"),
+           py::arg("Smax"), py::arg("num_cus"));
 
   auto dn = m.def_submodule("dense", "dense-layer bias gradients / fused GELU backward");
   dn.def("bias_grad", &bias_grad_op);

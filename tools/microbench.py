@@ -9,6 +9,7 @@
     python tools/microbench.py attn-packed  # packed (cu_seqlens) vs padded + key mask attention
     python tools/microbench.py attn-pairmask  # boolean [S, S] masks vs SDPA and the causal kernels
     python tools/microbench.py attn-gqa  # grouped-query heads vs expanded k / v, SDPA, equal heads
+    python tools/microbench.py attn-decode  # decode step over a KV cache vs SDPA, the byte floor
 """
 from __future__ import annotations
 
@@ -761,6 +762,60 @@ def bench_attn_gqa(args):
                 100 * (max(t) - min(t)) / med(t), med(t) / base), flush=True)
 
 
+HBM_PEAK = 8.0e12  # bytes/s: the MI355X's HBM3E peak as AMD publishes it
+
+
+def bench_attn_decode(args):
+    """One decode step over a KV cache (csrc/hip/attention_decode.hip): bf16, Sq = 1, every
+    batch element at length L in a cache of Smax = L rows, through the public op (split count
+    left to the host), against SDPA with enable_gqa=True on the [:L] slice, and against the
+    byte floor: the K and V rows the step must read, 2 * B * L * Hkv * D * 2 bytes, over
+    HBM_PEAK.  The variants alternate in one process over ROUNDS rounds after a warm-up; each
+    timed window ends in a device synchronise (timeit); prints medians, the spread (max - min)
+    / median, the K/V bytes per second the op achieved and its share of the peak."""
+    from apex_example_amd import _native
+    from apex_example_amd.ops import fused_attention_decode
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print("| shape (B x H / Hkv, D, L) | splits | decode us | spread | sdpa us | spread | "
+          "sdpa / decode | K/V TB/s | of HBM peak |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    shapes = [(b, 32, 8, 128, L) for L in (2048, 8192) for b in (1, 8, 64)]
+    shapes += [(8, 16, 16, 64, 1024), (8, 32, 1, 128, 4096)]
+    for b, h, hkv, d, L in shapes:
+        q = torch.randn(b, 1, h, d, device=dev, dtype=dt)
+        kv = torch.randn(b, L, 2, hkv, d, device=dev, dtype=dt)
+        lens = torch.full((b,), L, dtype=torch.int32, device=dev)
+        sq = q.transpose(1, 2)
+        sk, sv = (kv[:, :L, i].transpose(1, 2) for i in (0, 1))
+        kv_bytes = 2 * b * L * hkv * d * 2
+
+        def decode():
+            fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], lens)
+
+        def sdpa():
+            F.scaled_dot_product_attention(sq, sk, sv, enable_gqa=True)
+
+        variants = [("decode", decode), ("sdpa", sdpa)]
+        t_end = time.time() + 1.0  # clock / first-use ramp, as in bench_attn
+        while time.time() < t_end:
+            decode()
+            torch.cuda.synchronize()
+        times = {n: [] for n, _ in variants}
+        for _ in range(ROUNDS):
+            for n, fn in variants:
+                times[n].append(timeit(fn, iters=50, warmup=5))
+        med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+        spread = lambda xs: 100 * (max(xs) - min(xs)) / med(xs)  # noqa: E731
+        td, ts = med(times["decode"]), med(times["sdpa"])
+        rate = kv_bytes / (td * 1e-6)
+        print("| %d x %d / %d, %d, %d | %d | %.1f | %.1f %% | %.1f | %.1f %% | %.2f x | %.2f | "
+              "%.0f %% |" % (b, h, hkv, d, L, _native.require().attn.decode_splits(
+                  b, hkv, h // hkv, L, cus), td, spread(times["decode"]), ts,
+                  spread(times["sdpa"]), ts / td, rate / 1e12, 100 * rate / HBM_PEAK), flush=True)
+
+
 def bench_attn_packed(args):
     """Packed variable-length attention (fwd_varlen / bwd_varlen on the real tokens) against
     the padded [32, 512] call with the equivalent key-padding mask: B = 32 sequences with
@@ -1075,13 +1130,15 @@ def bench_conv1x1_stats(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
-                             "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa"])
+                             "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa",
+                             "attn-decode"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
      "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn,
      "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128,
-     "attn-pairmask": bench_attn_pairmask, "attn-gqa": bench_attn_gqa}[a.what](a)
+     "attn-pairmask": bench_attn_pairmask, "attn-gqa": bench_attn_gqa,
+     "attn-decode": bench_attn_decode}[a.what](a)
 
 
 if __name__ == "__main__":
