@@ -3,7 +3,8 @@ blocks with FusedLayerNorm, causal attention on the gfx950 fused attention
 kernels (ops/attention.py; PyTorch SDPA off-GPU / fp32),
 tanh-GELU MLP and an LM head tied to the token embedding.  ``generate`` samples with a
 ``KVCache``: the prompt runs through the causal kernels once, every further token through the
-split-KV decode kernels (``fused_attention_decode``).
+split-KV decode kernels (``fused_attention_decode``); with ``page_size`` the cache is a
+``PagedKVCache``, a page pool and a block table read by the paged decode kernels.
 
 gpt2_medium(): 24 layers, d_model 1024, 16 heads, vocab 50257, 1024 positions
 = 354,823,168 parameters in 292 tensors.
@@ -82,6 +83,45 @@ class KVCache:
             self.lengths += n
 
 
+class PagedKVCache:
+    """A ``KVCache`` kept in pages of ``page_size`` rows: per layer one packed pool [num_pages,
+    P, 2, Hkv, D] (allocated at the layer's first use) and, shared by the layers, one int32
+    block table [B, ceil(max_len / P)], built here with the pages of a sequence interleaved
+    across the batch (page(b, j) = j * B + b) and moved to the device with the first pool.
+    ``lengths`` / ``length`` / ``advance`` are those of ``KVCache``."""
+
+    def __init__(self, batch, max_len, page_size=64):
+        if page_size not in fused_attn.PAGE_SIZES:
+            raise ValueError("page_size must be one of %s, got %s" % (fused_attn.PAGE_SIZES,
+                                                                      page_size))
+        self.batch, self.max_len, self.page_size = int(batch), int(max_len), int(page_size)
+        self.max_pages = -(-self.max_len // self.page_size)
+        self.num_pages = self.batch * self.max_pages
+        self.block_table = (torch.arange(self.max_pages, dtype=torch.int32)[None] * self.batch
+                            + torch.arange(self.batch, dtype=torch.int32)[:, None]).contiguous()
+        self.kv = {}         # layer -> [num_pages, P, 2, Hkv, D]
+        self.lengths = None  # int32 [B], on the device of the first layer's pool
+        self.length = 0
+
+    def layer(self, idx, like):
+        """The pool of layer ``idx`` for keys shaped and typed like ``like`` [B, s, Hkv, D]."""
+        if idx not in self.kv:
+            self.kv[idx] = like.new_empty(self.num_pages, self.page_size, 2, like.size(2),
+                                          like.size(3))
+            if self.lengths is None:
+                self.lengths = torch.full((self.batch,), self.length, dtype=torch.int32,
+                                          device=like.device)
+                self.block_table = self.block_table.to(like.device)
+        return self.kv[idx]
+
+    def rows(self, lo, hi):
+        """(page ids [B, hi - lo], rows [hi - lo]) of keys lo .. hi - 1, as index tensors."""
+        pos = torch.arange(lo, hi, device=self.block_table.device)
+        return self.block_table[:, pos // self.page_size].long(), pos % self.page_size
+
+    advance = KVCache.advance
+
+
 class GPT2Attention(nn.Module):
     def __init__(self, cfg):
         super().__init__()
@@ -122,9 +162,11 @@ class GPT2Attention(nn.Module):
 
     def _cached(self, x, cache):
         """Attention output [b, s, e] of s new tokens behind the ``cache.length`` tokens of a
-        ``KVCache``, storing their keys and values (the model advances the lengths).  An empty
-        cache is a prefill on the causal kernels; a filled one a decode step, which appends in
-        its own launch.  Off the GPU / in fp32: SDPA over the filled rows."""
+        ``KVCache`` or ``PagedKVCache``, storing their keys and values (the model advances the
+        lengths).  An empty cache is a prefill on the causal kernels (a paged one stores the
+        prompt's rows through ``paged_kv_append``); a filled one a decode step, which appends in
+        its own launch.  Off the GPU / in fp32: SDPA over the filled rows (a paged cache's
+        gathered through the table)."""
         b, s, e = x.shape
         h, hkv, d = self.h, self.hkv or self.h, self.d
         y = self._lin(self.c_attn, x)
@@ -137,16 +179,25 @@ class GPT2Attention(nn.Module):
             raise ValueError("the KV cache holds %d x %d tokens: no room for batch %d, %d + %d "
                              "tokens" % (cache.batch, cache.max_len, b, L, s))
         kv = cache.layer(self.layer_idx, k)
+        paged = isinstance(cache, PagedKVCache)  # kv: [num_pages, P, 2, Hkv, D] behind a table
         fused = self.fused and fused_attn.supported(q, d)
         if fused and L > 0:
-            return fused_attn.fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], cache.lengths,
-                                                     k_new=k, v_new=v).view(b, s, e)
-        kv[:, L:L + s, 0] = k
-        kv[:, L:L + s, 1] = v
+            return fused_attn.fused_attention_decode(
+                q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v,
+                block_table=cache.block_table if paged else None).view(b, s, e)
+        if not paged:
+            kv[:, L:L + s, 0] = k
+            kv[:, L:L + s, 1] = v
+        elif fused:
+            fused_attn.paged_kv_append(k, v, kv[:, :, 0], kv[:, :, 1], cache.block_table,
+                                       cache.lengths)
+        else:
+            kv[cache.rows(L, L + s)] = torch.stack((k, v), 2)
         if fused:
             return fused_attn.fused_attention(q, k, v, causal=True).view(b, s, e)
         g = h // hkv
-        kk, vv = (kv[:, :L + s, i].transpose(1, 2).repeat_interleave(g, 1) for i in (0, 1))
+        filled = kv[cache.rows(0, L + s)] if paged else kv[:, :L + s]  # [b, L + s, 2, Hkv, D]
+        kk, vv = (filled[:, :, i].transpose(1, 2).repeat_interleave(g, 1) for i in (0, 1))
         # bottom-right causal mask: new token i sees keys j <= L + i
         keep = torch.ones(s, L + s, dtype=torch.bool, device=x.device).tril(L)
         o = F.scaled_dot_product_attention(q.transpose(1, 2), kk, vv, attn_mask=keep)
@@ -236,7 +287,7 @@ class GPT2LMHeadModel(nn.Module):
             nn.init.normal_(m.weight, std=self.config.initializer_range)
 
     def forward(self, input_ids, cache=None):
-        """Logits [B, S, vocab].  With a ``KVCache``, ``input_ids`` are the tokens that follow
+        """Logits [B, S, vocab].  With a ``KVCache`` / ``PagedKVCache``, ``input_ids`` are the tokens that follow
         the ``cache.length`` ones it holds: their keys and values are stored, their positions
         start at that length and they attend to everything before them (inference only)."""
         s = input_ids.size(1)
@@ -270,10 +321,11 @@ class GPT2LMHeadModel(nn.Module):
         return F.linear(y, self.wte.weight)  # tied LM head
 
     @torch.no_grad()
-    def generate(self, input_ids, max_new_tokens, temperature=0.0):
+    def generate(self, input_ids, max_new_tokens, temperature=0.0, page_size=None):
         """input_ids [B, S0] (one prompt length per batch) -> [B, S0 + max_new_tokens]: greedy
         at temperature 0, else sampled from softmax(logits / temperature).  Runs in eval mode
-        with a ``KVCache``: one forward over the prompt, then one token per step."""
+        with a ``KVCache`` or, with ``page_size``, a ``PagedKVCache`` of such pages: one forward
+        over the prompt, then one token per step."""
         b, s0 = input_ids.shape
         if s0 + max_new_tokens > self.config.n_positions:
             raise ValueError("%d prompt + %d new tokens exceed n_positions = %d" % (
@@ -281,7 +333,8 @@ class GPT2LMHeadModel(nn.Module):
         training = self.training
         self.eval()
         try:
-            cache = KVCache(b, s0 + max_new_tokens)
+            cache = KVCache(b, s0 + max_new_tokens) if page_size is None else \
+                PagedKVCache(b, s0 + max_new_tokens, page_size)
             out, step = input_ids, input_ids
             for n in range(max_new_tokens):
                 logits = self(step, cache=cache)[:, -1].float()

@@ -73,6 +73,18 @@ are read once per group, the four waves of a workgroup and ``num_splits`` workgr
 the keys, and a second launch joins the splits in a fixed order (bitwise reproducible for a
 given ``num_splits``).  docs/PERF.md, "Attention: decode over a KV cache".
 
+Paged KV cache: with ``block_table`` (int32 [B, max_pages] on the GPU) the caches of
+``fused_attention_decode`` are [num_pages, P, Hkv, D] page views of one pool (any strides: the
+halves of a packed [num_pages, P, 2, Hkv, D] pool; P in 16, 32, 64, 128, 256) and key j of
+batch element b is row j % P of page ``block_table[b][j // P]``, so memory follows the tokens
+held and sequences of any lengths share the pool.  The kernels (csrc/hip/
+attention_decode_paged.hip) walk the table in scalar registers one tile ahead of the K / V
+DMA; table entries at or past ceil(L_b / P) are never read, page ids are clamped to the pool,
+and a captured graph may be replayed after table entries are rewritten in place.  The work
+split is the contiguous kernels': for a given ``num_splits`` the result is bitwise that of the
+contiguous call on the same keys.  ``paged_kv_append`` stores new rows (a whole prompt at
+prefill) through the table on its own.  docs/PERF.md, "Attention: decode over a paged KV cache".
+
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size (the query and key lengths may differ) and H query heads over Hkv key/value heads
 with H % Hkv == 0 (Hkv < H neither with a pair mask nor packed), no mask other than
@@ -80,7 +92,8 @@ a per-batch key mask, a boolean pair mask (an additive [Tq, Tk] ``attn_mask`` is
 fused) or, at equal lengths, the causal mask; packed sequences ([T, H, D] with ``cu_seqlens``): q, k and v of one token
 and head count, self-attention per sequence, optional causal mask, no key mask.  A decode
 step over a KV cache (``fused_attention_decode``) takes the same dtypes, head dims and head
-groupings, forward only.  Callers
+groupings, forward only, over a contiguous cache or, with ``block_table``, over pages of
+16 to 256 rows.  Callers
 fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
 from __future__ import annotations
@@ -532,8 +545,106 @@ def fused_attention_varlen_qkv(qkv, cu_seqlens, max_seqlen=None, causal=False, d
                                    _seed(dropout_p), None, None, (cu_seqlens, max_seqlen), qkv)
 
 
+PAGE_SIZES = (16, 32, 64, 128, 256)  # the page sizes the paged decode kernels take
+
+
+def _check_paged(first, k_pages, v_pages, block_table, cache_seqlens):
+    """The pools, table and lengths of a paged call whose batch, dtype and device are those of
+    ``first`` = (name, [B, S, heads, D] tensor); ValueError on anything the kernels refuse."""
+    name0, t0 = first
+    for name, t in (first, ("k_pages", k_pages), ("v_pages", v_pages)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError("%s must be a 4-d tensor, got %s" % (
+                name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU, got a %s tensor" % (name, t.device))
+        if t.device != t0.device or t.dtype != t0.dtype:
+            raise ValueError("%s is %s on %s, %s %s on %s" % (name, t.dtype, t.device, name0,
+                                                             t0.dtype, t0.device))
+    if t0.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("decode takes bf16 / fp16 tensors, got %s" % t0.dtype)
+    B, D = t0.size(0), t0.size(3)
+    if D not in HEAD_DIMS:
+        raise ValueError("head dim must be one of %s, got %d" % (HEAD_DIMS, D))
+    if k_pages.shape != v_pages.shape or k_pages.size(3) != D:
+        raise ValueError("k_pages and v_pages must be [num_pages, P, Hkv, D] with D = %d, got %s "
+                         "and %s" % (D, tuple(k_pages.shape), tuple(v_pages.shape)))
+    P = k_pages.size(1)
+    if P not in PAGE_SIZES:
+        raise ValueError("the page size must be one of %s, got %d" % (PAGE_SIZES, P))
+    if k_pages.size(0) < 1:
+        raise ValueError("the page pool is empty")
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or \
+            block_table.dim() != 2 or block_table.size(0) != B or block_table.size(1) < 1:
+        raise ValueError("block_table must be an int32 [B, max_pages] = [%d, >= 1] tensor" % B)
+    if block_table.device != t0.device:
+        raise ValueError("block_table is on %s, %s on %s" % (block_table.device, name0,
+                                                            t0.device))
+    if not block_table.is_contiguous():
+        raise ValueError("block_table must be contiguous: the kernels read the tensor itself")
+    if block_table.size(1) * P >= 1 << 24:
+        raise ValueError("max_pages * page size must be below 2^24, got %d" % (
+            block_table.size(1) * P))
+    if any(P * t.stride(1) * 2 >= 1 << 32 for t in (k_pages, v_pages)):
+        raise ValueError("page size x row stride must stay below 2^32 bytes: the kernels' "
+                         "offsets within a page are 32-bit")
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or \
+            tuple(cache_seqlens.shape) != (B,):
+        raise ValueError("cache_seqlens must be an int32 [B] = [%d] tensor" % B)
+    if cache_seqlens.device != t0.device:
+        raise ValueError("cache_seqlens is on %s, %s on %s" % (cache_seqlens.device, name0,
+                                                              t0.device))
+    if not cache_seqlens.is_contiguous():
+        raise ValueError("cache_seqlens must be contiguous: the kernels read the tensor itself")
+
+
+def _check_new_rows(k_new, v_new, like, want):
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want or not t.is_cuda or \
+                t.device != like.device or t.dtype != like.dtype:
+            raise ValueError("%s must be a %s %s tensor on %s, got %s" % (
+                name, like.dtype, list(want), like.device,
+                (t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor)
+                else type(t).__name__))
+
+
+def _decode_paged(q, k_pages, v_pages, cache_seqlens, k_new, v_new, scale, num_splits,
+                  return_lse, block_table):
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new come as a pair")
+    _check_paged(("q", q), k_pages, v_pages, block_table, cache_seqlens)
+    _check_heads(q, k_pages)
+    B, Sq, _, D = q.shape
+    named = [q, k_pages, v_pages]
+    if k_new is not None:
+        _check_new_rows(k_new, v_new, q, (B, Sq, k_pages.size(2), D))
+        named += [k_new, v_new]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in named):
+        raise ValueError("fused_attention_decode is forward only: call it under torch.no_grad() "
+                         "or on detached tensors")
+    cap = _C().DECODE_MAX_SPLITS
+    if num_splits is not None and not 1 <= int(num_splits) <= cap:
+        raise ValueError("num_splits must be in [1, %d], got %s" % (cap, num_splits))
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    o, lse = _C().decode_paged(q, k_pages, v_pages, block_table, cache_seqlens, k_new, v_new,
+                               float(scale), 0 if num_splits is None else int(num_splits))
+    return (o, lse) if return_lse else o
+
+
+def paged_kv_append(k_new, v_new, k_pages, v_pages, block_table, cache_seqlens):
+    """Store k_new / v_new [B, Sn, Hkv, D] (any Sn: a prompt at prefill) in the pages of a paged
+    KV cache (``fused_attention_decode(..., block_table=)``): row i of batch element b becomes
+    key cache_seqlens[b] + i, row (cache_seqlens[b] + i) % P of page block_table[b][(cache_seqlens
+    [b] + i) // P].  Keys outside [0, max_pages * P) are skipped, page ids are clamped to the
+    pool.  One launch, no host sync; cache_seqlens is not advanced."""
+    _check_paged(("k_new", k_new), k_pages, v_pages, block_table, cache_seqlens)
+    want = (k_new.size(0), k_new.size(1), k_pages.size(2), k_new.size(3))
+    _check_new_rows(k_new, v_new, k_new, want)
+    _C().paged_append(k_new, v_new, k_pages, v_pages, block_table, cache_seqlens)
+
+
 def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None,
-                           scale=None, num_splits=None, return_lse=False):
+                           scale=None, num_splits=None, return_lse=False, block_table=None):
     """One decode step over a KV cache.  q: [B, Sq, H, D], the Sq newest tokens; k_cache,
     v_cache: [B, Smax, Hkv, D] views (any batch / sequence / head strides; H % Hkv == 0, D = 64
     or 128, bf16 / fp16); cache_seqlens: int32 [B] on the GPU, the keys already in the cache,
@@ -547,7 +658,17 @@ def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new
     num_splits: workgroups that split each cache (None: chosen from the shapes and the device's
     CU count, never from the lengths); results are bitwise reproducible for a given value.
     -> o [B, Sq, H, D] contiguous and, with return_lse, the fp32 [B, H, Sq] lse in log2 units.
-    Forward only: ValueError if a gradient is asked of it."""
+    Forward only: ValueError if a gradient is asked of it.
+
+    block_table: int32 [B, max_pages] on the GPU makes the cache a paged one: k_cache, v_cache
+    are then [num_pages, P, Hkv, D] page views of a pool (any page / row / head strides; P in
+    16, 32, 64, 128, 256), key j of batch element b is row j % P of page block_table[b][j // P],
+    Smax = max_pages * P, and k_new / v_new are appended through the table.  Entries at or
+    past ceil(L_b / P) are never read and page ids are clamped to the pool on the device.  For
+    a given num_splits the result is bitwise that of the contiguous call on the same keys."""
+    if block_table is not None:
+        return _decode_paged(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
+                             num_splits, return_lse, block_table)
     named = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)]
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new come as a pair")

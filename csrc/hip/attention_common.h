@@ -522,5 +522,9 @@ void attn_bwd_amask64(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 // both head dims with fewer key/value heads than query heads (attention_gqa.hip compiles them)
 void attn_fwd_gqa(const AttnProblem& p, void* o, float* lse, hipStream_t st);
 void attn_bwd_gqa(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
+// the fixed-order join of a decode step's split partials (attention_decode.hip), which the
+// paged decode kernels (attention_decode_paged.hip) share
+void attn_decode_combine(DType dtype, int D, int B, int H, int Sq, int nsplit, float* o_part,
+                         float* lse_part, void* o, float* lse, hipStream_t st);
 
 }  // namespace amd

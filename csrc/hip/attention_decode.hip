@@ -440,6 +440,24 @@ int attn_decode_splits(int B, int Hkv, int R, int Smax, int num_cus) {
   return n < 1 ? 1 : (int)n;
 }
 
+// attn_decode_combine_k on its own, for the paged kernels (attention_decode_paged.hip), whose
+// splits write the same workspace
+void attn_decode_combine(DType dtype, int D, int B, int H, int Sq, int nsplit, float* o_part,
+                         float* lse_part, void* o, float* lse, hipStream_t st) {
+  DecodeArgs a{};
+  a.o = o; a.lse = lse; a.o_part = o_part; a.lse_part = lse_part;
+  a.B = B; a.H = H; a.Sq = Sq;
+  const int64_t threads = (int64_t)B * Sq * H * (D / 4);
+  const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  if (dtype == DType::BF16) {
+    if (D == 64) hipLaunchKernelGGL((attn_decode_combine_k<bf16_t, 64>), grid, block, 0, st, a, nsplit);
+    else hipLaunchKernelGGL((attn_decode_combine_k<bf16_t, 128>), grid, block, 0, st, a, nsplit);
+  } else {
+    if (D == 64) hipLaunchKernelGGL((attn_decode_combine_k<half_t, 64>), grid, block, 0, st, a, nsplit);
+    else hipLaunchKernelGGL((attn_decode_combine_k<half_t, 128>), grid, block, 0, st, a, nsplit);
+  }
+}
+
 void attn_decode(const AttnDecode& p, void* o, float* lse, hipStream_t st) {
   if (p.D != 64 && p.D != 128) {
     fprintf(stderr, "attn_decode: head dim must be 64 or 128, got %d\n", p.D);

@@ -602,6 +602,24 @@ int attn_decode_splits(int B, int Hkv, int R, int Smax, int num_cus);
 // o [B][Sq][H][D] contiguous, lse [B][H][Sq] (log2 units)
 void attn_decode(const AttnDecode& p, void* o, float* lse, hipStream_t st);
 
+// The same decode step over a paged KV cache (attention_decode_paged.hip).  d.k / d.v are the
+// page pools [num_pages, P, Hkv, D] (sb = the page stride; any page / row / head strides), P =
+// 1 << log2_page in 16 .. 256; block_table is int32 [B][max_pages] on the device: key j of
+// batch element b is row j % P of page block_table[b][j / P].  d.Smax is not read: the table
+// spans max_pages * P keys, and that is what attn_decode_splits takes.  Page ids are clamped
+// to [0, num_pages - 1] on the device and entries at or past ceil(L_b / P) are never read.
+// P * row stride * 2 bytes must stay below 2^32 (the kernels' per-lane offsets are 32-bit).
+// For a given nsplit the result is bitwise that of attn_decode on the same keys.
+struct AttnDecodePaged {
+  AttnDecode d;
+  const int32_t* block_table = nullptr;
+  int num_pages = 0, max_pages = 0, log2_page = 0;
+};
+void attn_decode_paged(const AttnDecodePaged& p, void* o, float* lse, hipStream_t st);
+// the append alone: d.k_new / d.v_new [B, Sn, Hkv, D] to row (cache_seqlens[b] + i) % P of page
+// block_table[b][(cache_seqlens[b] + i) / P]; rows outside [0, max_pages * P) are skipped
+void attn_paged_append(const AttnDecodePaged& p, int Sn, hipStream_t st);
+
 // ---- fused softmax cross entropy with label smoothing (xentropy.hip) ---------
 // x [rows, V] row-major (T = fp32/fp16/bf16); loss [rows] (TO), lse [rows] fp32
 void xentropy_fwd(const void* x, DType tx, const int64_t* labels, int64_t rows, int V,

@@ -490,4 +490,143 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cac
   return {o, lse};
 }
 
+namespace {
+// The page pools and the table of a paged call, checked against B batch elements, Hkv heads
+// and head dim D of `like`'s dtype and device: P.d.k / v (sb = the page stride), the table
+// and the three page counts.  Returns Smax = max_pages * P.
+int64_t paged_views(AttnDecodePaged& P, const at::Tensor& k_pages, const at::Tensor& v_pages,
+                    const at::Tensor& block_table, const at::Tensor& like, int64_t B,
+                    const char* who) {
+  P.d.k = view_of(k_pages, "k_pages");
+  P.d.v = view_of(v_pages, "v_pages");
+  TORCH_CHECK(v_pages.sizes() == k_pages.sizes(), who, ": k_pages and v_pages shapes differ: ",
+              k_pages.sizes(), " and ", v_pages.sizes());
+  auto same = [&](const at::Tensor& t) {
+    return t.scalar_type() == like.scalar_type() && t.device() == like.device();
+  };
+  TORCH_CHECK((like.scalar_type() == at::kBFloat16 || like.scalar_type() == at::kHalf) &&
+                  same(k_pages) && same(v_pages),
+              who, ": bf16/fp16 tensors and pages of one dtype on one device");
+  const int64_t num_pages = k_pages.size(0), page = k_pages.size(1);
+  TORCH_CHECK(page == 16 || page == 32 || page == 64 || page == 128 || page == 256, who,
+              ": the page size must be 16, 32, 64, 128 or 256 rows, got ", page);
+  TORCH_CHECK(num_pages > 0 && num_pages < (int64_t{1} << 31), who, ": the pool holds ",
+              num_pages, " pages");
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == like.device() &&
+                  block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+                  block_table.size(0) == B && block_table.size(1) > 0 &&
+                  block_table.is_contiguous(),
+              who, ": block_table must be a contiguous int32 [B, max_pages] tensor on q's "
+              "device, got ", block_table.scalar_type(), " ", block_table.sizes());
+  const int64_t max_pages = block_table.size(1), Smax = max_pages * page;
+  TORCH_CHECK(Smax < (int64_t{1} << 24), who, ": max_pages * page size must be below 2^24");
+  // the kernels' per-lane byte offsets within a page are 32-bit
+  TORCH_CHECK(page * k_pages.stride(1) * 2 < (int64_t{1} << 32) &&
+                  page * v_pages.stride(1) * 2 < (int64_t{1} << 32),
+              who, ": page size x row stride must stay below 2^32 bytes");
+  P.block_table = block_table.data_ptr<int32_t>();
+  P.num_pages = (int)num_pages;
+  P.max_pages = (int)max_pages;
+  P.log2_page = 0;
+  while ((int64_t{1} << P.log2_page) < page) ++P.log2_page;
+  return Smax;
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor> attn_decode_paged_op(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages, at::Tensor block_table,
+    at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+    double scale, int64_t num_splits) {
+  c10::NoGradGuard no_grad_;
+  AttnDecodePaged PP;
+  AttnDecode& P = PP.d;
+  P.q = view_of(q, "q");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(k_pages.dim() == 4 && k_pages.size(3) == D && k_pages.size(2) > 0 &&
+                  H % k_pages.size(2) == 0,
+              "attn decode paged: q and the pages differ in head dim, or the heads do not "
+              "split: q ", q.sizes(), ", k_pages ", k_pages.sizes());
+  const int64_t Hkv = k_pages.size(2);
+  const int64_t Smax = paged_views(PP, k_pages, v_pages, block_table, q, B, "attn decode paged");
+  auto same = [&](const at::Tensor& t) {
+    return t.scalar_type() == q.scalar_type() && t.device() == q.device();
+  };
+  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == q.device() &&
+                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
+                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
+              "attn decode paged: cache_seqlens must be a contiguous int32 [B] tensor on q's "
+              "device, got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
+  TORCH_CHECK(k_new.has_value() == v_new.has_value(),
+              "attn decode paged: k_new and v_new come as a pair");
+  if (k_new.has_value()) {
+    P.k_new = view_of(*k_new, "k_new");
+    P.v_new = view_of(*v_new, "v_new");
+    const std::vector<int64_t> dims{B, Sq, Hkv, D};
+    const at::IntArrayRef want(dims);
+    TORCH_CHECK(k_new->sizes() == want && v_new->sizes() == want && same(*k_new) && same(*v_new),
+                "attn decode paged: k_new and v_new must be [B, Sq, Hkv, D] = ", want,
+                " of q's dtype and device, got ", k_new->sizes(), " and ", v_new->sizes());
+  }
+  TORCH_CHECK(Sq < (int64_t{1} << 24), "attn decode paged: Sq must be below 2^24");
+  const int64_t R = H / Hkv * Sq;
+  TORCH_CHECK(B * Hkv <= 65535 && (R + 31) / 32 <= 65535,
+              "attn decode paged: batch x key/value heads = ", B * Hkv, " or rows per group = ",
+              R, " exceeds a launch grid");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= kAttnDecodeMaxSplits,
+              "attn decode paged: num_splits must be in [1, ", kAttnDecodeMaxSplits, "], got ",
+              num_splits);
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
+  P.scale = (float)scale;
+  P.dtype = dtype_of(q);
+  at::Tensor o = at::empty({B, Sq, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (B == 0 || Sq == 0) return {o, lse};
+  int cus = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                    q.get_device()) == hipSuccess,
+              "attn decode paged: cannot read the device's CU count");
+  P.nsplit = num_splits > 0 ? (int)num_splits
+                            : attn_decode_splits(P.B, P.Hkv, (int)R, P.Smax, cus);
+  at::Tensor o_part, lse_part;
+  if (P.nsplit > 1) {
+    o_part = at::empty({P.nsplit, B, Sq, H, D}, q.options().dtype(at::kFloat));
+    lse_part = at::empty({P.nsplit, B, H, Sq}, q.options().dtype(at::kFloat));
+    P.o_part = o_part.data_ptr<float>();
+    P.lse_part = lse_part.data_ptr<float>();
+  }
+  attn_decode_paged(PP, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+void attn_paged_append_op(at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages,
+                          at::Tensor v_pages, at::Tensor block_table, at::Tensor cache_seqlens) {
+  c10::NoGradGuard no_grad_;
+  AttnDecodePaged PP;
+  AttnDecode& P = PP.d;
+  P.k_new = view_of(k_new, "k_new");
+  P.v_new = view_of(v_new, "v_new");
+  const int64_t B = k_new.size(0), Sn = k_new.size(1), Hkv = k_new.size(2), D = k_new.size(3);
+  TORCH_CHECK(v_new.sizes() == k_new.sizes() && v_new.scalar_type() == k_new.scalar_type() &&
+                  v_new.device() == k_new.device(),
+              "attn paged append: k_new and v_new differ: ", k_new.sizes(), " and ",
+              v_new.sizes());
+  TORCH_CHECK(k_pages.dim() == 4 && k_pages.size(2) == Hkv && k_pages.size(3) == D,
+              "attn paged append: the new rows and the pages differ in heads or head dim: ",
+              k_new.sizes(), " and ", k_pages.sizes());
+  paged_views(PP, k_pages, v_pages, block_table, k_new, B, "attn paged append");
+  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == k_new.device() &&
+                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
+                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
+              "attn paged append: cache_seqlens must be a contiguous int32 [B] tensor on the "
+              "rows' device, got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
+  TORCH_CHECK(Sn < (int64_t{1} << 24) && B * Sn * Hkv * (D / 8) < (int64_t{1} << 39),
+              "attn paged append: too many rows for one launch");
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.Hkv = (int)Hkv;
+  P.dtype = dtype_of(k_new);
+  if (B == 0 || Sn == 0) return;
+  attn_paged_append(PP, (int)Sn, cur_stream());
+}
+
 }  // namespace amd

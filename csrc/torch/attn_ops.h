@@ -93,4 +93,21 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cac
                                                   c10::optional<at::Tensor> v_new, double scale,
                                                   int64_t num_splits);
 
+// The same step over a paged KV cache (csrc/hip/attention_decode_paged.hip).  k_pages, v_pages:
+// [num_pages, P, Hkv, D] views (any page / row / head strides, head dim contiguous, 16-B
+// aligned rows, P in {16, 32, 64, 128, 256}, P x row stride below 2^32 bytes); block_table:
+// contiguous int32 [B, max_pages] on q's device, max_pages * P < 2^24: key j of batch element
+// b is row j % P of page block_table[b][j / P].  Page ids are clamped to the pool on the device
+// and entries at or past ceil(L_b / P) are never read.  Everything else as attn_decode_op,
+// whose result on the same keys this one equals bit for bit at the same num_splits.
+std::tuple<at::Tensor, at::Tensor> attn_decode_paged_op(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages, at::Tensor block_table,
+    at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+    double scale, int64_t num_splits);
+
+// The append alone: k_new / v_new [B, Sn, Hkv, D] (any Sn) into the pages at keys
+// cache_seqlens[b] + i; keys outside [0, max_pages * P) are skipped.  One launch, no host sync.
+void attn_paged_append_op(at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages,
+                          at::Tensor v_pages, at::Tensor block_table, at::Tensor cache_seqlens);
+
 }  // namespace amd

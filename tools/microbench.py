@@ -10,6 +10,7 @@
     python tools/microbench.py attn-pairmask  # boolean [S, S] masks vs SDPA and the causal kernels
     python tools/microbench.py attn-gqa  # grouped-query heads vs expanded k / v, SDPA, equal heads
     python tools/microbench.py attn-decode  # decode step over a KV cache vs SDPA, the byte floor
+    python tools/microbench.py attn-decode-paged  # ... over a paged cache vs the contiguous one
 """
 from __future__ import annotations
 
@@ -816,6 +817,66 @@ def bench_attn_decode(args):
                   spread(times["sdpa"]), ts / td, rate / 1e12, 100 * rate / HBM_PEAK), flush=True)
 
 
+def bench_attn_decode_paged(args):
+    """The decode step over a paged KV cache (csrc/hip/attention_decode_paged.hip) against the
+    contiguous one on the same keys: the shapes of bench_attn_decode, pages of 16, 64 and 256
+    rows, a shuffled block table over a pool of twice the pages the keys need, both through the
+    public op (split count left to the host: the same for both).  Paged and contiguous calls
+    alternate in one process over ROUNDS rounds after a warm-up; each timed window ends in a
+    device synchronise (timeit); prints medians, the spread (max - min) / median of each and
+    the ratio.  A paged time within the sum of the two spreads of the contiguous one counts
+    as equal."""
+    from apex_example_amd.ops import fused_attention_decode
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    print("| shape (B x H / Hkv, D, L) | P | paged us | spread | contiguous us | spread | "
+          "paged / contiguous | verdict |")
+    print("|---|---|---|---|---|---|---|---|")
+    shapes = [(b, 32, 8, 128, L) for L in (2048, 8192) for b in (1, 8, 64)]
+    shapes += [(8, 16, 16, 64, 1024), (8, 32, 1, 128, 4096)]
+    gen = torch.Generator().manual_seed(0)
+    for b, h, hkv, d, L in shapes:
+        q = torch.randn(b, 1, h, d, device=dev, dtype=dt)
+        kv = torch.randn(b, L, 2, hkv, d, device=dev, dtype=dt)
+        lens = torch.full((b,), L, dtype=torch.int32, device=dev)
+        for P in (16, 64, 256):
+            n = L // P
+            perm = torch.randperm(2 * b * n, generator=gen)[:b * n].to(dev)
+            pool = torch.zeros(2 * b * n, P, 2, hkv, d, device=dev, dtype=dt)
+            pool[perm] = kv.view(b * n, P, 2, hkv, d)
+            table = perm.view(b, n).int()
+
+            def paged():
+                fused_attention_decode(q, pool[:, :, 0], pool[:, :, 1], lens, block_table=table)
+
+            def contiguous():
+                fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], lens)
+
+            if not torch.equal(fused_attention_decode(q, pool[:, :, 0], pool[:, :, 1], lens,
+                                                      block_table=table),
+                               fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], lens)):
+                raise SystemExit("paged and contiguous outputs differ at %s" % ((b, h, hkv, d, L, P),))
+            variants = [("paged", paged), ("contiguous", contiguous)]
+            t_end = time.time() + 0.5  # clock / first-use ramp, as in bench_attn
+            while time.time() < t_end:
+                paged()
+                torch.cuda.synchronize()
+            times = {n_: [] for n_, _ in variants}
+            for _ in range(ROUNDS):
+                for n_, fn in variants:
+                    times[n_].append(timeit(fn, iters=50, warmup=5))
+            med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+            spread = lambda xs: (max(xs) - min(xs)) / med(xs)  # noqa: E731
+            tp, tc = med(times["paged"]), med(times["contiguous"])
+            sp, sc = spread(times["paged"]), spread(times["contiguous"])
+            verdict = "equal" if abs(tp - tc) <= (sp + sc) * tc else (
+                "slower" if tp > tc else "faster")
+            print("| %d x %d / %d, %d, %d | %d | %.1f | %.1f %% | %.1f | %.1f %% | %.3f x | %s |"
+                  % (b, h, hkv, d, L, P, tp, 100 * sp, tc, 100 * sc, tp / tc, verdict),
+                  flush=True)
+            del pool
+
+
 def bench_attn_packed(args):
     """Packed variable-length attention (fwd_varlen / bwd_varlen on the real tokens) against
     the padded [32, 512] call with the equivalent key-padding mask: B = 32 sequences with
@@ -1131,14 +1192,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
                              "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa",
-                             "attn-decode"])
+                             "attn-decode", "attn-decode-paged"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
      "conv3x3": bench_conv3x3, "conv-s2": bench_conv_s2, "attn": bench_attn,
      "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128,
      "attn-pairmask": bench_attn_pairmask, "attn-gqa": bench_attn_gqa,
-     "attn-decode": bench_attn_decode}[a.what](a)
+     "attn-decode": bench_attn_decode,
+     "attn-decode-paged": bench_attn_decode_paged}[a.what](a)
 
 
 if __name__ == "__main__":
