@@ -4,7 +4,8 @@ kernels (ops/attention.py; PyTorch SDPA off-GPU / fp32),
 tanh-GELU MLP and an LM head tied to the token embedding.  ``generate`` samples with a
 ``KVCache``: the prompt runs through the causal kernels once, every further token through the
 split-KV decode kernels (``fused_attention_decode``); with ``page_size`` the cache is a
-``PagedKVCache``, a page pool and a block table read by the paged decode kernels.
+``PagedKVCache``, a page pool and a block table read by the paged decode kernels; with
+``kv_dtype=torch.float8_e4m3fn`` the ``KVCache`` holds FP8 rows and one fp32 scale per row.
 
 gpt2_medium(): 24 layers, d_model 1024, 16 heads, vocab 50257, 1024 positions
 = 354,823,168 parameters in 292 tensors.
@@ -59,18 +60,27 @@ class KVCache:
     first use, in its activations' dtype), one int32 [B] length tensor on the device, which the
     decode kernels read, and the same length as a host integer, so that choosing between the
     prefill and the decode path costs no sync.  One length per batch: ragged prompts are not
-    served."""
+    served.  With ``kv_dtype=torch.float8_e4m3fn`` a layer's buffer is FP8 and comes with fp32
+    per-row scales [B, 2, Hkv, max_len] (``scales``): half the bytes a decode step reads."""
 
-    def __init__(self, batch, max_len):
-        self.batch, self.max_len = int(batch), int(max_len)
+    def __init__(self, batch, max_len, kv_dtype=None):
+        if kv_dtype not in (None, fused_attn.FP8):
+            raise ValueError("kv_dtype must be None (the activations' dtype) or "
+                             "torch.float8_e4m3fn, got %s" % kv_dtype)
+        self.batch, self.max_len, self.kv_dtype = int(batch), int(max_len), kv_dtype
         self.kv = {}         # layer -> [B, max_len, 2, Hkv, D]
+        self.scales = {}     # FP8: layer -> fp32 [B, 2, Hkv, max_len]
         self.lengths = None  # int32 [B], on the device of the first layer's buffer
         self.length = 0
 
     def layer(self, idx, like):
         """The buffer of layer ``idx`` for keys shaped and typed like ``like`` [B, s, Hkv, D]."""
         if idx not in self.kv:
-            self.kv[idx] = like.new_empty(self.batch, self.max_len, 2, like.size(2), like.size(3))
+            self.kv[idx] = like.new_empty(self.batch, self.max_len, 2, like.size(2), like.size(3),
+                                          dtype=self.kv_dtype or like.dtype)
+            if self.kv_dtype is not None:
+                self.scales[idx] = like.new_empty(self.batch, 2, like.size(2), self.max_len,
+                                                  dtype=torch.float32)
             if self.lengths is None:
                 self.lengths = torch.full((self.batch,), self.length, dtype=torch.int32,
                                           device=like.device)
@@ -88,9 +98,14 @@ class PagedKVCache:
     P, 2, Hkv, D] (allocated at the layer's first use) and, shared by the layers, one int32
     block table [B, ceil(max_len / P)], built here with the pages of a sequence interleaved
     across the batch (page(b, j) = j * B + b) and moved to the device with the first pool.
-    ``lengths`` / ``length`` / ``advance`` are those of ``KVCache``."""
+    ``lengths`` / ``length`` / ``advance`` are those of ``KVCache``.  16-bit pages only: an FP8
+    cache (``kv_dtype``) is not paged yet."""
+    kv_dtype = None
 
-    def __init__(self, batch, max_len, page_size=64):
+    def __init__(self, batch, max_len, page_size=64, kv_dtype=None):
+        if kv_dtype is not None:
+            raise ValueError("a paged KV cache holds the activations' dtype: kv_dtype = %s is "
+                             "served by the contiguous KVCache only" % kv_dtype)
         if page_size not in fused_attn.PAGE_SIZES:
             raise ValueError("page_size must be one of %s, got %s" % (fused_attn.PAGE_SIZES,
                                                                       page_size))
@@ -166,7 +181,10 @@ class GPT2Attention(nn.Module):
         lengths).  An empty cache is a prefill on the causal kernels (a paged one stores the
         prompt's rows through ``paged_kv_append``); a filled one a decode step, which appends in
         its own launch.  Off the GPU / in fp32: SDPA over the filled rows (a paged cache's
-        gathered through the table)."""
+        gathered through the table).  An FP8 cache: the new rows are quantised on their way in
+        (``fp8_kv_append`` or the decode call's own append; off the kernels by their torch
+        mirror ``fp8_quantize_rows``), a decode step attends the quantised rows, its own
+        included, and a prefill the prompt's own 16-bit keys and values, on either path."""
         b, s, e = x.shape
         h, hkv, d = self.h, self.hkv or self.h, self.d
         y = self._lin(self.c_attn, x)
@@ -181,11 +199,21 @@ class GPT2Attention(nn.Module):
         kv = cache.layer(self.layer_idx, k)
         paged = isinstance(cache, PagedKVCache)  # kv: [num_pages, P, 2, Hkv, D] behind a table
         fused = self.fused and fused_attn.supported(q, d)
+        sc = cache.scales[self.layer_idx] if cache.kv_dtype is not None else None
         if fused and L > 0:
             return fused_attn.fused_attention_decode(
                 q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v,
-                block_table=cache.block_table if paged else None).view(b, s, e)
-        if not paged:
+                block_table=cache.block_table if paged else None,
+                k_scale=None if sc is None else sc[:, 0],
+                v_scale=None if sc is None else sc[:, 1]).view(b, s, e)
+        if sc is not None and fused:
+            fused_attn.fp8_kv_append(k, v, kv[:, :, 0], kv[:, :, 1], sc[:, 0], sc[:, 1],
+                                     cache.lengths)
+        elif sc is not None:
+            for i, t in enumerate((k, v)):
+                kv[:, L:L + s, i], rows = fused_attn.fp8_quantize_rows(t)
+                sc[:, i, :, L:L + s] = rows.transpose(1, 2)
+        elif not paged:
             kv[:, L:L + s, 0] = k
             kv[:, L:L + s, 1] = v
         elif fused:
@@ -197,6 +225,11 @@ class GPT2Attention(nn.Module):
             return fused_attn.fused_attention(q, k, v, causal=True).view(b, s, e)
         g = h // hkv
         filled = kv[cache.rows(0, L + s)] if paged else kv[:, :L + s]  # [b, L + s, 2, Hkv, D]
+        if sc is not None and L == 0:
+            filled = torch.stack((k, v), 2)
+        elif sc is not None:
+            rows = sc[..., :L + s].permute(0, 3, 1, 2).unsqueeze(-1)  # [b, L + s, 2, Hkv, 1]
+            filled = (filled.float() * rows).to(q.dtype)
         kk, vv = (filled[:, :, i].transpose(1, 2).repeat_interleave(g, 1) for i in (0, 1))
         # bottom-right causal mask: new token i sees keys j <= L + i
         keep = torch.ones(s, L + s, dtype=torch.bool, device=x.device).tril(L)
@@ -321,11 +354,12 @@ class GPT2LMHeadModel(nn.Module):
         return F.linear(y, self.wte.weight)  # tied LM head
 
     @torch.no_grad()
-    def generate(self, input_ids, max_new_tokens, temperature=0.0, page_size=None):
+    def generate(self, input_ids, max_new_tokens, temperature=0.0, page_size=None, kv_dtype=None):
         """input_ids [B, S0] (one prompt length per batch) -> [B, S0 + max_new_tokens]: greedy
         at temperature 0, else sampled from softmax(logits / temperature).  Runs in eval mode
         with a ``KVCache`` or, with ``page_size``, a ``PagedKVCache`` of such pages: one forward
-        over the prompt, then one token per step."""
+        over the prompt, then one token per step.  ``kv_dtype=torch.float8_e4m3fn`` keeps the
+        (contiguous) cache in FP8 with per-row scales."""
         b, s0 = input_ids.shape
         if s0 + max_new_tokens > self.config.n_positions:
             raise ValueError("%d prompt + %d new tokens exceed n_positions = %d" % (
@@ -333,8 +367,8 @@ class GPT2LMHeadModel(nn.Module):
         training = self.training
         self.eval()
         try:
-            cache = KVCache(b, s0 + max_new_tokens) if page_size is None else \
-                PagedKVCache(b, s0 + max_new_tokens, page_size)
+            cache = KVCache(b, s0 + max_new_tokens, kv_dtype) if page_size is None else \
+                PagedKVCache(b, s0 + max_new_tokens, page_size, kv_dtype)
             out, step = input_ids, input_ids
             for n in range(max_new_tokens):
                 logits = self(step, cache=cache)[:, -1].float()

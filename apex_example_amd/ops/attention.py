@@ -85,6 +85,16 @@ split is the contiguous kernels': for a given ``num_splits`` the result is bitwi
 contiguous call on the same keys.  ``paged_kv_append`` stores new rows (a whole prompt at
 prefill) through the table on its own.  docs/PERF.md, "Attention: decode over a paged KV cache".
 
+FP8 KV cache: with ``torch.float8_e4m3fn`` caches and ``k_scale`` / ``v_scale`` (fp32 [B, Hkv,
+Smax], one scale per batch element, key/value head and key) ``fused_attention_decode`` reads
+half the K / V bytes: key j of head hk is ``k_cache[b, j, hk].float() * k_scale[b, hk, j]``.
+q, o and the new rows stay bf16 / fp16 and so do the MFMAs; the kernels (csrc/hip/
+attention_decode_fp8.hip) turn the bytes into 16-bit fragments in registers (exact) and apply
+the scales to the scores and to p, so quantisation is the only error the format adds.
+``k_new`` / ``v_new`` are quantised per row by the append kernel (scale = amax / 448), as
+``fp8_kv_append`` does on its own and ``fp8_quantize_rows`` mirrors in torch bit for bit.  Not
+paged yet.  docs/PERF.md, "Attention: decode over an FP8 KV cache".
+
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size (the query and key lengths may differ) and H query heads over Hkv key/value heads
 with H % Hkv == 0 (Hkv < H neither with a pair mask nor packed), no mask other than
@@ -93,7 +103,8 @@ fused) or, at equal lengths, the causal mask; packed sequences ([T, H, D] with `
 and head count, self-attention per sequence, optional causal mask, no key mask.  A decode
 step over a KV cache (``fused_attention_decode``) takes the same dtypes, head dims and head
 groupings, forward only, over a contiguous cache or, with ``block_table``, over pages of
-16 to 256 rows.  Callers
+16 to 256 rows; a contiguous cache may instead be float8_e4m3fn with fp32 per-row scales (q
+still bf16 / fp16).  Callers
 fall back to ``F.scaled_dot_product_attention`` otherwise.
 """
 from __future__ import annotations
@@ -643,8 +654,102 @@ def paged_kv_append(k_new, v_new, k_pages, v_pages, block_table, cache_seqlens):
     _C().paged_append(k_new, v_new, k_pages, v_pages, block_table, cache_seqlens)
 
 
+FP8 = torch.float8_e4m3fn  # the one 8-bit cache dtype (OCP e4m3: finite up to 448, no inf)
+
+
+def fp8_quantize_rows(x):
+    """The quantiser of the FP8 KV cache in plain torch, bit for bit the append kernel's: per
+    row (last dim) scale = amax / 448 in fp32 (1.0 for an all-zero row) and bytes = e4m3_rne(
+    clamp(x / scale, -448, 448)).  -> (float8_e4m3fn like x, fp32 scales x.shape[:-1])."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    return (xf / scale.unsqueeze(-1)).clamp(-448.0, 448.0).to(FP8), scale
+
+
+def _check_fp8(first, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table=None):
+    """The caches, scales and lengths of an FP8 call whose batch, 16-bit dtype and device are
+    those of ``first`` = (name, [B, S, heads, D] tensor); ValueError on anything refused."""
+    name0, t0 = first
+    if block_table is not None:
+        raise ValueError("an FP8 KV cache is not paged yet: block_table takes bf16 / fp16 pages")
+    for name, t in (first, ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError("%s must be a 4-d tensor, got %s" % (
+                name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not t.is_cuda or t.device != t0.device:
+            raise ValueError("%s must be on %s's GPU, got a %s tensor" % (name, name0, t.device))
+    if k_cache.dtype != FP8 or v_cache.dtype != FP8:
+        if k_cache.dtype.itemsize > 1 and v_cache.dtype.itemsize > 1:
+            raise ValueError("k_scale / v_scale come with a float8_e4m3fn cache, not with %s"
+                             % k_cache.dtype)
+        raise ValueError("an 8-bit KV cache is float8_e4m3fn in both halves, got %s and %s" % (
+            k_cache.dtype, v_cache.dtype))
+    if t0.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("decode takes bf16 / fp16 %s, got %s" % (name0, t0.dtype))
+    B, D = t0.size(0), t0.size(3)
+    if D not in HEAD_DIMS:
+        raise ValueError("head dim must be one of %s, got %d" % (HEAD_DIMS, D))
+    if k_cache.shape != v_cache.shape or k_cache.size(0) != B or k_cache.size(3) != D:
+        raise ValueError("k_cache and v_cache must be [B, Smax, Hkv, D] with B = %d, D = %d, got "
+                         "%s and %s" % (B, D, tuple(k_cache.shape), tuple(v_cache.shape)))
+    want = (B, k_cache.size(2), k_cache.size(1))
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or \
+                tuple(t.shape) != want or t.device != t0.device or t.stride(2) != 1:
+            raise ValueError("%s must be an fp32 [B, Hkv, Smax] = %s tensor on %s with the key "
+                             "index contiguous, got %s" % (
+                                 name, list(want), t0.device,
+                                 (t.dtype, tuple(t.shape), t.stride(), t.device)
+                                 if isinstance(t, torch.Tensor) else type(t).__name__))
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or \
+            tuple(cache_seqlens.shape) != (B,):
+        raise ValueError("cache_seqlens must be an int32 [B] = [%d] tensor" % B)
+    if cache_seqlens.device != t0.device:
+        raise ValueError("cache_seqlens is on %s, %s on %s" % (cache_seqlens.device, name0,
+                                                              t0.device))
+    if not cache_seqlens.is_contiguous():
+        raise ValueError("cache_seqlens must be contiguous: the kernels read the tensor itself")
+
+
+def _decode_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, num_splits,
+                return_lse, block_table, k_scale, v_scale):
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new come as a pair")
+    _check_fp8(("q", q), k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table)
+    _check_heads(q, k_cache)
+    B, Sq, _, D = q.shape
+    named = [q]
+    if k_new is not None:
+        _check_new_rows(k_new, v_new, q, (B, Sq, k_cache.size(2), D))
+        named += [k_new, v_new]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in named):
+        raise ValueError("fused_attention_decode is forward only: call it under torch.no_grad() "
+                         "or on detached tensors")
+    cap = _C().DECODE_MAX_SPLITS
+    if num_splits is not None and not 1 <= int(num_splits) <= cap:
+        raise ValueError("num_splits must be in [1, %d], got %s" % (cap, num_splits))
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    o, lse = _C().decode_fp8(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, k_new, v_new,
+                             float(scale), 0 if num_splits is None else int(num_splits))
+    return (o, lse) if return_lse else o
+
+
+def fp8_kv_append(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens):
+    """Quantise k_new / v_new [B, Sn, Hkv, D] (bf16 / fp16, any Sn: a prompt at prefill) into an
+    FP8 KV cache (``fused_attention_decode(..., k_scale=, v_scale=)``): row i of batch element b
+    becomes key cache_seqlens[b] + i, its bytes and its scale as ``fp8_quantize_rows`` gives
+    them.  Keys outside [0, Smax) are skipped.  One launch, no host sync; cache_seqlens is not
+    advanced."""
+    _check_fp8(("k_new", k_new), k_cache, v_cache, k_scale, v_scale, cache_seqlens)
+    want = (k_new.size(0), k_new.size(1), k_cache.size(2), k_new.size(3))
+    _check_new_rows(k_new, v_new, k_new, want)
+    _C().fp8_append(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens)
+
+
 def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None,
-                           scale=None, num_splits=None, return_lse=False, block_table=None):
+                           scale=None, num_splits=None, return_lse=False, block_table=None,
+                           k_scale=None, v_scale=None):
     """One decode step over a KV cache.  q: [B, Sq, H, D], the Sq newest tokens; k_cache,
     v_cache: [B, Smax, Hkv, D] views (any batch / sequence / head strides; H % Hkv == 0, D = 64
     or 128, bf16 / fp16); cache_seqlens: int32 [B] on the GPU, the keys already in the cache,
@@ -665,7 +770,19 @@ def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new
     16, 32, 64, 128, 256), key j of batch element b is row j % P of page block_table[b][j // P],
     Smax = max_pages * P, and k_new / v_new are appended through the table.  Entries at or
     past ceil(L_b / P) are never read and page ids are clamped to the pool on the device.  For
-    a given num_splits the result is bitwise that of the contiguous call on the same keys."""
+    a given num_splits the result is bitwise that of the contiguous call on the same keys.
+
+    k_scale, v_scale: with float8_e4m3fn k_cache and v_cache (both), the fp32 [B, Hkv, Smax]
+    per-row scales (key index contiguous, any batch / head strides: the halves of one [B, 2, Hkv,
+    Smax] buffer): key j of head hk is k_cache[b, j, hk].float() * k_scale[b, hk, j].  q, k_new
+    and v_new stay bf16 / fp16; k_new / v_new are quantised per row on their way in
+    (``fp8_quantize_rows``), and everything above holds.  ValueError without the scales, with
+    scales on a 16-bit cache, with caches of two dtypes or another 8-bit dtype, and with
+    block_table: the paged FP8 cache is not built yet (the follow-up to this path)."""
+    if k_scale is not None or v_scale is not None or any(
+            isinstance(t, torch.Tensor) and t.dtype.itemsize == 1 for t in (k_cache, v_cache)):
+        return _decode_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, num_splits,
+                           return_lse, block_table, k_scale, v_scale)
     if block_table is not None:
         return _decode_paged(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
                              num_splits, return_lse, block_table)

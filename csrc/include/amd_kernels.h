@@ -620,6 +620,24 @@ void attn_decode_paged(const AttnDecodePaged& p, void* o, float* lse, hipStream_
 // block_table[b][(cache_seqlens[b] + i) / P]; rows outside [0, max_pages * P) are skipped
 void attn_paged_append(const AttnDecodePaged& p, int Sn, hipStream_t st);
 
+// The same decode step over an FP8 KV cache (attention_decode_fp8.hip).  d.k / d.v are OCP e4m3
+// bytes [B, Smax, Hkv, D] (strides in bytes, multiples of 16; 16-byte aligned), k_scale /
+// v_scale fp32 [B][Hkv][Smax] with the key index contiguous (sb / sh: batch and head strides in
+// floats): key j of head hk is d.k[b][j][hk][:] * k_scale[b][hk][j].  d.q, d.k_new, d.v_new and
+// o are 16-bit of d.dtype.  Bytes and scales at or past L_b are never read.  Split choice,
+// workspace and join are attn_decode's.
+struct AttnDecodeFp8 {
+  AttnDecode d;
+  float* k_scale = nullptr;
+  float* v_scale = nullptr;
+  int64_t ks_sb = 0, ks_sh = 0, vs_sb = 0, vs_sh = 0;
+};
+void attn_decode_fp8(const AttnDecodeFp8& p, void* o, float* lse, hipStream_t st);
+// the quantising append alone: d.k_new / d.v_new [B, Sn, Hkv, D] to rows cache_seqlens[b] + i
+// (rows outside [0, d.Smax) are skipped): per row scale = amax / 448 (1.0 for an all-zero row),
+// byte = e4m3_rne(clamp(x / scale, -448, 448))
+void attn_fp8_append(const AttnDecodeFp8& p, int Sn, hipStream_t st);
+
 // ---- fused softmax cross entropy with label smoothing (xentropy.hip) ---------
 // x [rows, V] row-major (T = fp32/fp16/bf16); loss [rows] (TO), lse [rows] fp32
 void xentropy_fwd(const void* x, DType tx, const int64_t* labels, int64_t rows, int V,

@@ -629,4 +629,138 @@ void attn_paged_append_op(at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages
   attn_paged_append(PP, (int)Sn, cur_stream());
 }
 
+namespace {
+// The FP8 caches and their scales, checked against B batch elements, Hkv heads and head dim D
+// on `like`'s device: P.d.k / v (byte strides), the scale pointers and strides.  Returns Smax.
+int64_t fp8_views(AttnDecodeFp8& P, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                  const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& like,
+                  int64_t B, int64_t Hkv, int64_t D, const char* who) {
+  for (const at::Tensor* t : {&k_cache, &v_cache}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() && t->dim() == 4 &&
+                    t->scalar_type() == at::kFloat8_e4m3fn,
+                who, ": the caches must be float8_e4m3fn [B, Smax, Hkv, D] tensors on the GPU");
+    TORCH_CHECK(t->stride(3) == 1 && ((uintptr_t)t->data_ptr() % 16) == 0 &&
+                    t->stride(0) % 16 == 0 && t->stride(1) % 16 == 0 && t->stride(2) % 16 == 0,
+                who, ": the caches need a contiguous head dim and 16-byte aligned rows");
+    TORCH_CHECK(t->stride(1) >= 0 && t->stride(1) < (int64_t{1} << 24), who,
+                ": the caches' sequence stride must be below 2^24 bytes");
+  }
+  TORCH_CHECK(head_dim_ok(D) && k_cache.size(0) == B && k_cache.size(2) == Hkv &&
+                  k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes(),
+              who, ": k_cache and v_cache must be [B, Smax, Hkv, D] = [", B, ", Smax, ", Hkv,
+              ", ", D, "], got ", k_cache.sizes(), " and ", v_cache.sizes());
+  const int64_t Smax = k_cache.size(1);
+  TORCH_CHECK(Smax < (int64_t{1} << 24), who, ": Smax must be below 2^24");
+  for (const at::Tensor* t : {&k_scale, &v_scale})
+    TORCH_CHECK(t->is_cuda() && t->device() == like.device() &&
+                    t->scalar_type() == at::kFloat && t->dim() == 3 && t->size(0) == B &&
+                    t->size(1) == Hkv && t->size(2) == Smax && t->stride(2) == 1,
+                who, ": k_scale and v_scale must be fp32 [B, Hkv, Smax] = [", B, ", ", Hkv, ", ",
+                Smax, "] with the key index contiguous, on the caches' device, got ", t->sizes());
+  P.d.k = {k_cache.data_ptr(), k_cache.stride(0), k_cache.stride(1), k_cache.stride(2)};
+  P.d.v = {v_cache.data_ptr(), v_cache.stride(0), v_cache.stride(1), v_cache.stride(2)};
+  P.k_scale = k_scale.data_ptr<float>(); P.ks_sb = k_scale.stride(0); P.ks_sh = k_scale.stride(1);
+  P.v_scale = v_scale.data_ptr<float>(); P.vs_sb = v_scale.stride(0); P.vs_sh = v_scale.stride(1);
+  return Smax;
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
+    at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale,
+    at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+    double scale, int64_t num_splits) {
+  c10::NoGradGuard no_grad_;
+  AttnDecodeFp8 PP;
+  AttnDecode& P = PP.d;
+  P.q = view_of(q, "q");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf,
+              "attn decode fp8: q must be bf16 or fp16");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) > 0 && H % k_cache.size(2) == 0,
+              "attn decode fp8: the heads do not split: q ", q.sizes(), ", k_cache ",
+              k_cache.sizes());
+  const int64_t Hkv = k_cache.size(2);
+  const int64_t Smax = fp8_views(PP, k_cache, v_cache, k_scale, v_scale, q, B, Hkv, D,
+                                 "attn decode fp8");
+  auto same = [&](const at::Tensor& t) {
+    return t.scalar_type() == q.scalar_type() && t.device() == q.device();
+  };
+  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == q.device() &&
+                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
+                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
+              "attn decode fp8: cache_seqlens must be a contiguous int32 [B] tensor on q's "
+              "device, got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
+  TORCH_CHECK(k_new.has_value() == v_new.has_value(),
+              "attn decode fp8: k_new and v_new come as a pair");
+  if (k_new.has_value()) {
+    P.k_new = view_of(*k_new, "k_new");
+    P.v_new = view_of(*v_new, "v_new");
+    const std::vector<int64_t> dims{B, Sq, Hkv, D};
+    const at::IntArrayRef want(dims);
+    TORCH_CHECK(k_new->sizes() == want && v_new->sizes() == want && same(*k_new) && same(*v_new),
+                "attn decode fp8: k_new and v_new must be [B, Sq, Hkv, D] = ", want,
+                " of q's dtype and device, got ", k_new->sizes(), " and ", v_new->sizes());
+  }
+  TORCH_CHECK(Sq < (int64_t{1} << 24), "attn decode fp8: Sq must be below 2^24");
+  const int64_t R = H / Hkv * Sq;
+  TORCH_CHECK(B * Hkv <= 65535 && (R + 31) / 32 <= 65535,
+              "attn decode fp8: batch x key/value heads = ", B * Hkv, " or rows per group = ", R,
+              " exceeds a launch grid");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= kAttnDecodeMaxSplits,
+              "attn decode fp8: num_splits must be in [1, ", kAttnDecodeMaxSplits, "], got ",
+              num_splits);
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
+  P.scale = (float)scale;
+  P.dtype = dtype_of(q);
+  at::Tensor o = at::empty({B, Sq, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (B == 0 || Sq == 0) return {o, lse};
+  int cus = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                                    q.get_device()) == hipSuccess,
+              "attn decode fp8: cannot read the device's CU count");
+  P.nsplit = num_splits > 0 ? (int)num_splits
+                            : attn_decode_splits(P.B, P.Hkv, (int)R, P.Smax, cus);
+  at::Tensor o_part, lse_part;
+  if (P.nsplit > 1) {
+    o_part = at::empty({P.nsplit, B, Sq, H, D}, q.options().dtype(at::kFloat));
+    lse_part = at::empty({P.nsplit, B, H, Sq}, q.options().dtype(at::kFloat));
+    P.o_part = o_part.data_ptr<float>();
+    P.lse_part = lse_part.data_ptr<float>();
+  }
+  attn_decode_fp8(PP, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+void attn_fp8_append_op(at::Tensor k_new, at::Tensor v_new, at::Tensor k_cache,
+                        at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale,
+                        at::Tensor cache_seqlens) {
+  c10::NoGradGuard no_grad_;
+  AttnDecodeFp8 PP;
+  AttnDecode& P = PP.d;
+  P.k_new = view_of(k_new, "k_new");
+  P.v_new = view_of(v_new, "v_new");
+  const int64_t B = k_new.size(0), Sn = k_new.size(1), Hkv = k_new.size(2), D = k_new.size(3);
+  TORCH_CHECK((k_new.scalar_type() == at::kBFloat16 || k_new.scalar_type() == at::kHalf) &&
+                  v_new.sizes() == k_new.sizes() && v_new.scalar_type() == k_new.scalar_type() &&
+                  v_new.device() == k_new.device(),
+              "attn fp8 append: k_new and v_new must be bf16 / fp16 tensors of one shape, dtype "
+              "and device, got ", k_new.sizes(), " and ", v_new.sizes());
+  const int64_t Smax = fp8_views(PP, k_cache, v_cache, k_scale, v_scale, k_new, B, Hkv, D,
+                                 "attn fp8 append");
+  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == k_new.device() &&
+                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
+                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
+              "attn fp8 append: cache_seqlens must be a contiguous int32 [B] tensor on the "
+              "rows' device, got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
+  TORCH_CHECK(Sn < (int64_t{1} << 24) && B * Sn * Hkv * (D / 8) < (int64_t{1} << 39),
+              "attn fp8 append: too many rows for one launch");
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.Hkv = (int)Hkv; P.Smax = (int)Smax;
+  P.dtype = dtype_of(k_new);
+  if (B == 0 || Sn == 0) return;
+  attn_fp8_append(PP, (int)Sn, cur_stream());
+}
+
 }  // namespace amd

@@ -110,4 +110,22 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_paged_op(
 void attn_paged_append_op(at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages,
                           at::Tensor v_pages, at::Tensor block_table, at::Tensor cache_seqlens);
 
+// The decode step over an FP8 KV cache (csrc/hip/attention_decode_fp8.hip).  k_cache, v_cache:
+// float8_e4m3fn [B, Smax, Hkv, D] views (any batch / sequence / head strides that are multiples
+// of 16 bytes, head dim contiguous, 16-B aligned); k_scale, v_scale: fp32 [B, Hkv, Smax] views
+// with the key index contiguous (any batch / head strides); q and k_new / v_new: one bf16 / fp16
+// dtype.  k_new / v_new are quantised per row on their way into the cache.  Everything else as
+// attn_decode_op.
+std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
+    at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale,
+    at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+    double scale, int64_t num_splits);
+
+// The quantising append alone: k_new / v_new [B, Sn, Hkv, D] (bf16 / fp16, any Sn) into cache
+// rows cache_seqlens[b] + i and their scales; rows outside [0, Smax) are skipped.  One launch,
+// no host sync.
+void attn_fp8_append_op(at::Tensor k_new, at::Tensor v_new, at::Tensor k_cache,
+                        at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale,
+                        at::Tensor cache_seqlens);
+
 }  // namespace amd

@@ -135,6 +135,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   attn.def("paged_append", &attn_paged_append_op, py::arg("k_new"), py::arg("v_new"),
            py::arg("k_pages"), py::arg("v_pages"), py::arg("block_table"),
            py::arg("cache_seqlens"));
+  attn.def("decode_fp8", &attn_decode_fp8_op, py::arg("q"), py::arg("k_cache"),
+           py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cache_seqlens"),
+           py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("scale") = 1.0,
+           py::arg("num_splits") = 0);
+  attn.def("fp8_append", &attn_fp8_append_op, py::arg("k_new"), py::arg("v_new"),
+           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"),
+           py::arg("cache_seqlens"));
   attn.attr("DECODE_MAX_SPLITS") = kAttnDecodeMaxSplits;
   attn.def("decode_splits", &attn_decode_splits, py::arg("B"), py::arg("Hkv"), py::arg("R"),
            py::arg("Smax"), py::arg("num_cus"));

@@ -11,6 +11,7 @@
     python tools/microbench.py attn-gqa  # grouped-query heads vs expanded k / v, SDPA, equal heads
     python tools/microbench.py attn-decode  # decode step over a KV cache vs SDPA, the byte floor
     python tools/microbench.py attn-decode-paged  # ... over a paged cache vs the contiguous one
+    python tools/microbench.py attn-decode-fp8  # ... over an FP8 cache vs the 16-bit one
 """
 from __future__ import annotations
 
@@ -877,6 +878,61 @@ def bench_attn_decode_paged(args):
             del pool
 
 
+def bench_attn_decode_fp8(args):
+    """The decode step over an FP8 KV cache (csrc/hip/attention_decode_fp8.hip) against the
+    16-bit one: the shapes of bench_attn_decode, the FP8 cache quantised from the same bf16 keys
+    by fp8_kv_append, both through the public op (split count left to the host: the same for
+    both).  The two calls alternate in one process over ROUNDS rounds of 50 calls after a
+    warm-up; each timed window ends in a device synchronise (timeit); prints medians, the
+    spread (max - min) / median of each, the ratio, the FP8 byte floor 2 * B * L * Hkv * (D + 4)
+    bytes (rows and scales) over HBM_PEAK and the share of the peak the FP8 call achieved.  An
+    FP8 time within the sum of the two spreads of the 16-bit one counts as equal."""
+    from apex_example_amd.ops import fp8_kv_append, fused_attention_decode
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    print("| shape (B x H / Hkv, D, L) | fp8 us | spread | 16-bit us | spread | 16-bit / fp8 | "
+          "verdict | fp8 floor us | fp8 K/V TB/s | of HBM peak |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    shapes = [(b, 32, 8, 128, L) for L in (2048, 8192) for b in (1, 8, 64)]
+    shapes += [(8, 16, 16, 64, 1024), (8, 32, 1, 128, 4096)]
+    for b, h, hkv, d, L in shapes:
+        q = torch.randn(b, 1, h, d, device=dev, dtype=dt)
+        kv = torch.randn(b, L, 2, hkv, d, device=dev, dtype=dt)
+        kv8 = torch.empty(b, L, 2, hkv, d, device=dev, dtype=torch.float8_e4m3fn)
+        sc = torch.empty(b, 2, hkv, L, device=dev, dtype=torch.float32)
+        lens = torch.full((b,), L, dtype=torch.int32, device=dev)
+        fp8_kv_append(kv[:, :, 0], kv[:, :, 1], kv8[:, :, 0], kv8[:, :, 1], sc[:, 0], sc[:, 1],
+                      torch.zeros_like(lens))
+        fp8_bytes = 2 * b * L * hkv * (d + 4)
+
+        def fp8():
+            fused_attention_decode(q, kv8[:, :, 0], kv8[:, :, 1], lens, k_scale=sc[:, 0],
+                                   v_scale=sc[:, 1])
+
+        def wide():
+            fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], lens)
+
+        variants = [("fp8", fp8), ("wide", wide)]
+        t_end = time.time() + 0.5  # clock / first-use ramp, as in bench_attn
+        while time.time() < t_end:
+            fp8()
+            torch.cuda.synchronize()
+        times = {n: [] for n, _ in variants}
+        for _ in range(ROUNDS):
+            for n, fn in variants:
+                times[n].append(timeit(fn, iters=50, warmup=5))
+        med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+        spread = lambda xs: (max(xs) - min(xs)) / med(xs)  # noqa: E731
+        tf, tw = med(times["fp8"]), med(times["wide"])
+        sf, sw = spread(times["fp8"]), spread(times["wide"])
+        verdict = "equal" if abs(tf - tw) <= (sf + sw) * tw else ("slower" if tf > tw else "faster")
+        rate = fp8_bytes / (tf * 1e-6)
+        print("| %d x %d / %d, %d, %d | %.1f | %.1f %% | %.1f | %.1f %% | %.2f x | %s | %.1f | "
+              "%.2f | %.0f %% |" % (b, h, hkv, d, L, tf, 100 * sf, tw, 100 * sw, tw / tf, verdict,
+                                    fp8_bytes / HBM_PEAK * 1e6, rate / 1e12,
+                                    100 * rate / HBM_PEAK), flush=True)
+
+
 def bench_attn_packed(args):
     """Packed variable-length attention (fwd_varlen / bwd_varlen on the real tokens) against
     the padded [32, 512] call with the equivalent key-padding mask: B = 32 sequences with
@@ -1192,7 +1248,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
                              "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa",
-                             "attn-decode", "attn-decode-paged"])
+                             "attn-decode", "attn-decode-paged", "attn-decode-fp8"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
@@ -1200,7 +1256,8 @@ def main():
      "attn-packed": bench_attn_packed, "attn-d128": bench_attn_d128,
      "attn-pairmask": bench_attn_pairmask, "attn-gqa": bench_attn_gqa,
      "attn-decode": bench_attn_decode,
-     "attn-decode-paged": bench_attn_decode_paged}[a.what](a)
+     "attn-decode-paged": bench_attn_decode_paged,
+     "attn-decode-fp8": bench_attn_decode_fp8}[a.what](a)
 
 
 if __name__ == "__main__":
