@@ -3,7 +3,9 @@ blocks with FusedLayerNorm, causal attention on the gfx950 fused attention
 kernels (ops/attention.py; PyTorch SDPA off-GPU / fp32),
 tanh-GELU MLP and an LM head tied to the token embedding.  ``generate`` samples with a
 ``KVCache``: the prompt runs through the causal kernels once, every further token through the
-split-KV decode kernels (``fused_attention_decode``); with ``page_size`` the cache is a
+split-KV decode kernels (``fused_attention_decode``), later chunks of a prompt fed in pieces
+(``prefill_chunk``) through the chunked-prefill kernels (``fused_attention_prefill``); with
+``page_size`` the cache is a
 ``PagedKVCache``, a page pool and a block table read by the paged decode kernels; with
 ``kv_dtype=torch.float8_e4m3fn`` the ``KVCache`` holds FP8 rows and one fp32 scale per row.
 
@@ -46,6 +48,14 @@ class GPT2Config:
     # residual add + dropout + the next LayerNorm as one kernel per sublayer join
     # (fp32 residual stream, 16-bit sublayer output under O1)
     fused_residual_ln: bool = True
+
+
+# New rows (tokens x query heads of a group) from which a chunk behind a filled contiguous 16-bit
+# cache goes to the chunked-prefill kernels instead of the decode kernels: the smallest measured
+# row count at which they beat decode at every measured cache length (docs/PERF.md, "Attention:
+# chunked prefill over a KV cache": below it decode's split-KV wins at batch 1; the section also
+# names the small grids above it where decode is still faster).
+PREFILL_MIN_ROWS = 2048
 
 
 def _ln(cfg, n):
@@ -180,9 +190,10 @@ class GPT2Attention(nn.Module):
         ``KVCache`` or ``PagedKVCache``, storing their keys and values (the model advances the
         lengths).  An empty cache is a prefill on the causal kernels (a paged one stores the
         prompt's rows through ``paged_kv_append``); a filled one a decode step, which appends in
-        its own launch.  Off the GPU / in fp32: SDPA over the filled rows (a paged cache's
-        gathered through the table).  An FP8 cache: the new rows are quantised on their way in
-        (``fp8_kv_append`` or the decode call's own append; off the kernels by their torch
+        its own launch - or, for a contiguous 16-bit cache and s * (h / hkv) >= PREFILL_MIN_ROWS
+        new rows, a chunk on the chunked-prefill kernels, which append the same way.  Off the
+        GPU / in fp32: SDPA over the filled rows (a paged cache's gathered through the table).
+        An FP8 cache: the new rows are quantised on their way in (``fp8_kv_append`` or the decode call's own append; off the kernels by their torch
         mirror ``fp8_quantize_rows``), a decode step attends the quantised rows, its own
         included, and a prefill the prompt's own 16-bit keys and values, on either path."""
         b, s, e = x.shape
@@ -200,6 +211,9 @@ class GPT2Attention(nn.Module):
         paged = isinstance(cache, PagedKVCache)  # kv: [num_pages, P, 2, Hkv, D] behind a table
         fused = self.fused and fused_attn.supported(q, d)
         sc = cache.scales[self.layer_idx] if cache.kv_dtype is not None else None
+        if fused and L > 0 and not paged and sc is None and s * (h // hkv) >= PREFILL_MIN_ROWS:
+            return fused_attn.fused_attention_prefill(
+                q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v).view(b, s, e)
         if fused and L > 0:
             return fused_attn.fused_attention_decode(
                 q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v,
@@ -354,13 +368,18 @@ class GPT2LMHeadModel(nn.Module):
         return F.linear(y, self.wte.weight)  # tied LM head
 
     @torch.no_grad()
-    def generate(self, input_ids, max_new_tokens, temperature=0.0, page_size=None, kv_dtype=None):
+    def generate(self, input_ids, max_new_tokens, temperature=0.0, page_size=None, kv_dtype=None,
+                 prefill_chunk=None):
         """input_ids [B, S0] (one prompt length per batch) -> [B, S0 + max_new_tokens]: greedy
         at temperature 0, else sampled from softmax(logits / temperature).  Runs in eval mode
         with a ``KVCache`` or, with ``page_size``, a ``PagedKVCache`` of such pages: one forward
         over the prompt, then one token per step.  ``kv_dtype=torch.float8_e4m3fn`` keeps the
-        (contiguous) cache in FP8 with per-row scales."""
+        (contiguous) cache in FP8 with per-row scales.  ``prefill_chunk``: feed the prompt in
+        chunks of that many tokens (bounded activation memory for a long prompt), the first on
+        the causal kernels, the later ones behind the filled cache; None: one forward."""
         b, s0 = input_ids.shape
+        if prefill_chunk is not None and prefill_chunk < 1:
+            raise ValueError("prefill_chunk must be a positive token count, got %s" % prefill_chunk)
         if s0 + max_new_tokens > self.config.n_positions:
             raise ValueError("%d prompt + %d new tokens exceed n_positions = %d" % (
                 s0, max_new_tokens, self.config.n_positions))
@@ -370,6 +389,11 @@ class GPT2LMHeadModel(nn.Module):
             cache = KVCache(b, s0 + max_new_tokens, kv_dtype) if page_size is None else \
                 PagedKVCache(b, s0 + max_new_tokens, page_size, kv_dtype)
             out, step = input_ids, input_ids
+            if prefill_chunk is not None and max_new_tokens > 0:
+                # all but the last chunk of the prompt: only their keys and values are needed
+                while s0 - cache.length > prefill_chunk:
+                    self(input_ids[:, cache.length:cache.length + prefill_chunk], cache=cache)
+                step = input_ids[:, cache.length:]
             for n in range(max_new_tokens):
                 logits = self(step, cache=cache)[:, -1].float()
                 if temperature > 0.0:

@@ -95,6 +95,17 @@ the scales to the scores and to p, so quantisation is the only error the format 
 ``fp8_kv_append`` does on its own and ``fp8_quantize_rows`` mirrors in torch bit for bit.  Not
 paged yet.  docs/PERF.md, "Attention: decode over an FP8 KV cache".
 
+Chunked prefill over a KV cache: ``fused_attention_prefill(q, k_cache, v_cache, cache_seqlens)``
+is the decode call for many new tokens (a later chunk of a long prompt, the next turn of a
+conversation, a prompt behind a shared prefix) over a contiguous bf16 / fp16 cache: the same
+tensors, lengths on the device, bottom-right mask, clip and ``k_new`` / ``v_new`` append, but
+kernels (csrc/hip/attention_prefill.hip) that split the rows instead of the keys: the G * Sq rows
+of a key/value head's group in token order, 128 per workgroup, every 64-key K / V tile shared by
+four waves through LDS, each workgroup's key loop ending at the last key its tokens see.  One
+launch, no ``num_splits``, bitwise reproducible.  It wins where the row tiles fill the device
+and loses to decode's split-KV where they do not (B = 1 with a few hundred rows): docs/PERF.md,
+"Attention: chunked prefill over a KV cache".  Paged and FP8 caches are refused here.
+
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size (the query and key lengths may differ) and H query heads over Hkv key/value heads
 with H % Hkv == 0 (Hkv < H neither with a pair mask nor packed), no mask other than
@@ -747,6 +758,49 @@ def fp8_kv_append(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlen
     _C().fp8_append(k_new, v_new, k_cache, v_cache, k_scale, v_scale, cache_seqlens)
 
 
+def _check_cache16(what, q, k_cache, v_cache, cache_seqlens, k_new, v_new):
+    """The tensors of a call over a contiguous 16-bit KV cache (``what``: "decode" or
+    "prefill"), ValueError on anything refused; -> the head dim."""
+    named = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)]
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new come as a pair")
+    if k_new is not None:
+        named += [("k_new", k_new), ("v_new", v_new)]
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError("%s must be a 4-d tensor, got %s" % (
+                name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if not t.is_cuda:
+            raise ValueError("%s must be on the GPU, got a %s tensor" % (name, t.device))
+        if t.device != q.device or t.dtype != q.dtype:
+            raise ValueError("%s is %s on %s, q %s on %s" % (name, t.dtype, t.device, q.dtype,
+                                                            q.device))
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("%s takes bf16 / fp16 tensors, got %s" % (what, q.dtype))
+    B, Sq, H, D = q.shape
+    if D not in HEAD_DIMS:
+        raise ValueError("head dim must be one of %s, got %d" % (HEAD_DIMS, D))
+    if k_cache.shape != v_cache.shape or k_cache.size(0) != B or k_cache.size(3) != D:
+        raise ValueError("k_cache and v_cache must be [B, Smax, Hkv, D] with B = %d, D = %d, got "
+                         "%s and %s" % (B, D, tuple(k_cache.shape), tuple(v_cache.shape)))
+    _check_heads(q, k_cache)
+    Hkv = k_cache.size(2)
+    if k_new is not None and not (tuple(k_new.shape) == tuple(v_new.shape) == (B, Sq, Hkv, D)):
+        raise ValueError("k_new and v_new must be [B, Sq, Hkv, D] = [%d, %d, %d, %d], got %s and "
+                         "%s" % (B, Sq, Hkv, D, tuple(k_new.shape), tuple(v_new.shape)))
+    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or \
+            tuple(cache_seqlens.shape) != (B,):
+        raise ValueError("cache_seqlens must be an int32 [B] = [%d] tensor" % B)
+    if cache_seqlens.device != q.device:
+        raise ValueError("cache_seqlens is on %s, q on %s" % (cache_seqlens.device, q.device))
+    if not cache_seqlens.is_contiguous():
+        raise ValueError("cache_seqlens must be contiguous: the kernels read the tensor itself")
+    if torch.is_grad_enabled() and any(t.requires_grad for _, t in named):
+        raise ValueError("fused_attention_%s is forward only: call it under torch.no_grad() "
+                         "or on detached tensors" % what)
+    return D
+
+
 def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None,
                            scale=None, num_splits=None, return_lse=False, block_table=None,
                            k_scale=None, v_scale=None):
@@ -786,47 +840,39 @@ def fused_attention_decode(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new
     if block_table is not None:
         return _decode_paged(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
                              num_splits, return_lse, block_table)
-    named = [("q", q), ("k_cache", k_cache), ("v_cache", v_cache)]
-    if (k_new is None) != (v_new is None):
-        raise ValueError("k_new and v_new come as a pair")
-    if k_new is not None:
-        named += [("k_new", k_new), ("v_new", v_new)]
-    for name, t in named:
-        if not isinstance(t, torch.Tensor) or t.dim() != 4:
-            raise ValueError("%s must be a 4-d tensor, got %s" % (
-                name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
-        if not t.is_cuda:
-            raise ValueError("%s must be on the GPU, got a %s tensor" % (name, t.device))
-        if t.device != q.device or t.dtype != q.dtype:
-            raise ValueError("%s is %s on %s, q %s on %s" % (name, t.dtype, t.device, q.dtype,
-                                                            q.device))
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("decode takes bf16 / fp16 tensors, got %s" % q.dtype)
-    B, Sq, H, D = q.shape
-    if D not in HEAD_DIMS:
-        raise ValueError("head dim must be one of %s, got %d" % (HEAD_DIMS, D))
-    if k_cache.shape != v_cache.shape or k_cache.size(0) != B or k_cache.size(3) != D:
-        raise ValueError("k_cache and v_cache must be [B, Smax, Hkv, D] with B = %d, D = %d, got "
-                         "%s and %s" % (B, D, tuple(k_cache.shape), tuple(v_cache.shape)))
-    _check_heads(q, k_cache)
-    Hkv = k_cache.size(2)
-    if k_new is not None and not (tuple(k_new.shape) == tuple(v_new.shape) == (B, Sq, Hkv, D)):
-        raise ValueError("k_new and v_new must be [B, Sq, Hkv, D] = [%d, %d, %d, %d], got %s and "
-                         "%s" % (B, Sq, Hkv, D, tuple(k_new.shape), tuple(v_new.shape)))
-    if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or \
-            tuple(cache_seqlens.shape) != (B,):
-        raise ValueError("cache_seqlens must be an int32 [B] = [%d] tensor" % B)
-    if cache_seqlens.device != q.device:
-        raise ValueError("cache_seqlens is on %s, q on %s" % (cache_seqlens.device, q.device))
-    if not cache_seqlens.is_contiguous():
-        raise ValueError("cache_seqlens must be contiguous: the kernels read the tensor itself")
-    if torch.is_grad_enabled() and any(t.requires_grad for _, t in named):
-        raise ValueError("fused_attention_decode is forward only: call it under torch.no_grad() "
-                         "or on detached tensors")
+    D = _check_cache16("decode", q, k_cache, v_cache, cache_seqlens, k_new, v_new)
     cap = _C().DECODE_MAX_SPLITS
     if num_splits is not None and not 1 <= int(num_splits) <= cap:
         raise ValueError("num_splits must be in [1, %d], got %s" % (cap, num_splits))
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     o, lse = _C().decode(q, k_cache, v_cache, cache_seqlens, k_new, v_new, float(scale),
                          0 if num_splits is None else int(num_splits))
+    return (o, lse) if return_lse else o
+
+
+def fused_attention_prefill(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None,
+                            scale=None, return_lse=False, block_table=None, k_scale=None,
+                            v_scale=None):
+    """Sq new tokens (a prompt chunk, the next turn, a draft: any Sq >= 1) over a contiguous
+    bf16 / fp16 KV cache that holds a prefix.  Every tensor and every contract is
+    ``fused_attention_decode``'s: q [B, Sq, H, D]; k_cache, v_cache [B, Smax, Hkv, D] views;
+    cache_seqlens int32 [B] on the GPU, read by the kernels only; with k_new and v_new [B, Sq,
+    Hkv, D] the rows are first stored at rows cache_seqlens[b] + i and L_b = cache_seqlens[b] +
+    Sq, else L_b = cache_seqlens[b], clipped to Smax on the device; query i sees keys j <= L_b -
+    Sq + i, a query that sees no key gets o = 0 and lse = -inf; cache_seqlens is not advanced.
+    -> o [B, Sq, H, D] contiguous and, with return_lse, the fp32 [B, H, Sq] lse in log2 units.
+    One launch without a workspace: there is no num_splits and results are bitwise
+    reproducible.  Forward only.  ValueError for an 8-bit cache (or scales) and for a
+    block_table: this op serves the contiguous 16-bit cache only, those go to
+    ``fused_attention_decode``."""
+    if k_scale is not None or v_scale is not None or any(
+            isinstance(t, torch.Tensor) and t.dtype.itemsize == 1 for t in (k_cache, v_cache)):
+        raise ValueError("fused_attention_prefill takes a bf16 / fp16 KV cache: an 8-bit cache "
+                         "(k_scale / v_scale) is served by fused_attention_decode only")
+    if block_table is not None:
+        raise ValueError("fused_attention_prefill takes a contiguous KV cache: a paged one "
+                         "(block_table) is served by fused_attention_decode only")
+    D = _check_cache16("prefill", q, k_cache, v_cache, cache_seqlens, k_new, v_new)
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    o, lse = _C().prefill(q, k_cache, v_cache, cache_seqlens, k_new, v_new, float(scale))
     return (o, lse) if return_lse else o

@@ -526,5 +526,8 @@ void attn_bwd_gqa(const AttnProblem& p, const AttnBwd& g, hipStream_t st);
 // paged decode kernels (attention_decode_paged.hip) share
 void attn_decode_combine(DType dtype, int D, int B, int H, int Sq, int nsplit, float* o_part,
                          float* lse_part, void* o, float* lse, hipStream_t st);
+// the append of a decode step alone (attention_decode.hip; nothing without k_new / v_new), which
+// the prefill kernels (attention_prefill.hip) share
+void attn_decode_append(const AttnDecode& p, hipStream_t st);
 
 }  // namespace amd

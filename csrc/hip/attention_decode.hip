@@ -458,6 +458,23 @@ void attn_decode_combine(DType dtype, int D, int B, int H, int Sq, int nsplit, f
   }
 }
 
+// attn_decode_append_k on its own: p.k_new / p.v_new (none: nothing is launched) to cache rows
+// cache_seqlens[b] + i, for attn_decode below and the prefill kernels (attention_prefill.hip)
+void attn_decode_append(const AttnDecode& p, hipStream_t st) {
+  if (p.k_new.p == nullptr) return;
+  AppendArgs c{};
+  c.kn = p.k_new.p; c.knsb = p.k_new.sb; c.knss = p.k_new.ss; c.knsh = p.k_new.sh;
+  c.vn = p.v_new.p; c.vnsb = p.v_new.sb; c.vnss = p.v_new.ss; c.vnsh = p.v_new.sh;
+  c.kc = p.k.p; c.kcsb = p.k.sb; c.kcss = p.k.ss; c.kcsh = p.k.sh;
+  c.vc = p.v.p; c.vcsb = p.v.sb; c.vcss = p.v.ss; c.vcsh = p.v.sh;
+  c.lens = p.cache_seqlens;
+  c.B = p.B; c.Sq = p.Sq; c.Hkv = p.Hkv; c.Smax = p.Smax;
+  const int64_t threads = (int64_t)p.B * p.Sq * p.Hkv * (p.D / 8);
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  if (p.D == 64) hipLaunchKernelGGL((attn_decode_append_k<64>), grid, block, 0, st, c);
+  else hipLaunchKernelGGL((attn_decode_append_k<128>), grid, block, 0, st, c);
+}
+
 void attn_decode(const AttnDecode& p, void* o, float* lse, hipStream_t st) {
   if (p.D != 64 && p.D != 128) {
     fprintf(stderr, "attn_decode: head dim must be 64 or 128, got %d\n", p.D);
@@ -475,19 +492,7 @@ void attn_decode(const AttnDecode& p, void* o, float* lse, hipStream_t st) {
     abort();
   }
   if (p.B <= 0 || p.Sq <= 0) return;
-  if (p.k_new.p != nullptr) {
-    AppendArgs c{};
-    c.kn = p.k_new.p; c.knsb = p.k_new.sb; c.knss = p.k_new.ss; c.knsh = p.k_new.sh;
-    c.vn = p.v_new.p; c.vnsb = p.v_new.sb; c.vnss = p.v_new.ss; c.vnsh = p.v_new.sh;
-    c.kc = p.k.p; c.kcsb = p.k.sb; c.kcss = p.k.ss; c.kcsh = p.k.sh;
-    c.vc = p.v.p; c.vcsb = p.v.sb; c.vcss = p.v.ss; c.vcsh = p.v.sh;
-    c.lens = p.cache_seqlens;
-    c.B = p.B; c.Sq = p.Sq; c.Hkv = p.Hkv; c.Smax = p.Smax;
-    const int64_t threads = (int64_t)p.B * p.Sq * p.Hkv * (p.D / 8);
-    dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-    if (p.D == 64) hipLaunchKernelGGL((attn_decode_append_k<64>), grid, block, 0, st, c);
-    else hipLaunchKernelGGL((attn_decode_append_k<128>), grid, block, 0, st, c);
-  }
+  attn_decode_append(p, st);
   DecodeArgs a{};
   a.q = p.q.p; a.qsb = p.q.sb; a.qss = p.q.ss; a.qsh = p.q.sh;
   a.k = p.k.p; a.ksb = p.k.sb; a.kss = p.k.ss; a.ksh = p.k.sh;

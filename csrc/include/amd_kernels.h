@@ -638,6 +638,19 @@ void attn_decode_fp8(const AttnDecodeFp8& p, void* o, float* lse, hipStream_t st
 // byte = e4m3_rne(clamp(x / scale, -448, 448))
 void attn_fp8_append(const AttnDecodeFp8& p, int Sn, hipStream_t st);
 
+// Chunked prefill over a contiguous 16-bit KV cache (attention_prefill.hip): the problem, the
+// lengths, the bottom-right mask and the append are attn_decode's, for any Sq - the kernels
+// split the G * Sq rows (token-major, 128 per workgroup) instead of the keys, share each K / V
+// tile between the four waves and stop at the last key a row tile sees.  One launch: d.nsplit,
+// d.o_part and d.lse_part are not read.  Launch limits (attn_prefill aborts beyond them): at most
+// 2^23 row tiles ceil(G * Sq / 128), Hkv and B at most 65535, tiles * Hkv * B below 2^31.
+// Bitwise reproducible.
+struct AttnPrefill {
+  AttnDecode d;
+};
+// o [B][Sq][H][D] contiguous, lse [B][H][Sq] (log2 units)
+void attn_prefill(const AttnPrefill& p, void* o, float* lse, hipStream_t st);
+
 // ---- fused softmax cross entropy with label smoothing (xentropy.hip) ---------
 // x [rows, V] row-major (T = fp32/fp16/bf16); loss [rows] (TO), lse [rows] fp32
 void xentropy_fwd(const void* x, DType tx, const int64_t* labels, int64_t rows, int V,

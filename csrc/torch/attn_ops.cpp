@@ -418,47 +418,65 @@ void attn_bwd_varlen_op(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor 
   attn_bwd(F, G, cur_stream());
 }
 
-std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cache,
-                                                  at::Tensor v_cache, at::Tensor cache_seqlens,
-                                                  c10::optional<at::Tensor> k_new,
-                                                  c10::optional<at::Tensor> v_new, double scale,
-                                                  int64_t num_splits) {
-  c10::NoGradGuard no_grad_;
+namespace {
+// The problem of a call over a contiguous 16-bit KV cache (attn_decode_op, attn_prefill_op),
+// checked: views, shapes, one dtype and device, the lengths tensor, paired new rows.  `who`
+// opens the messages.
+AttnDecode cache_problem(const char* who, const at::Tensor& q, const at::Tensor& k_cache,
+                         const at::Tensor& v_cache, const at::Tensor& cache_seqlens,
+                         const c10::optional<at::Tensor>& k_new,
+                         const c10::optional<at::Tensor>& v_new, double scale) {
   AttnDecode P;
   P.q = view_of(q, "q");
   P.k = view_of(k_cache, "k_cache");
   P.v = view_of(v_cache, "v_cache");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "attn decode: k_cache and v_cache shapes "
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), who, ": k_cache and v_cache shapes "
               "differ: ", k_cache.sizes(), " and ", v_cache.sizes());
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
   const int64_t Smax = k_cache.size(1), Hkv = k_cache.size(2);
   TORCH_CHECK(k_cache.size(0) == B && k_cache.size(3) == D && Hkv > 0 && H % Hkv == 0,
-              "attn decode: q and the caches differ in batch or head dim, or the heads do not "
+              who, ": q and the caches differ in batch or head dim, or the heads do not "
               "split: q ", q.sizes(), ", k_cache ", k_cache.sizes());
   auto same = [&](const at::Tensor& t) {
     return t.scalar_type() == q.scalar_type() && t.device() == q.device();
   };
   TORCH_CHECK((q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf) &&
                   same(k_cache) && same(v_cache),
-              "attn decode: bf16/fp16 q and caches of one dtype on one device");
+              who, ": bf16/fp16 q and caches of one dtype on one device");
   TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == q.device() &&
                   cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
                   cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
-              "attn decode: cache_seqlens must be a contiguous int32 [B] tensor on q's device, "
+              who, ": cache_seqlens must be a contiguous int32 [B] tensor on q's device, "
               "got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
-  TORCH_CHECK(k_new.has_value() == v_new.has_value(),
-              "attn decode: k_new and v_new come as a pair");
+  TORCH_CHECK(k_new.has_value() == v_new.has_value(), who, ": k_new and v_new come as a pair");
   if (k_new.has_value()) {
     P.k_new = view_of(*k_new, "k_new");
     P.v_new = view_of(*v_new, "v_new");
     const std::vector<int64_t> dims{B, Sq, Hkv, D};
     const at::IntArrayRef want(dims);
     TORCH_CHECK(k_new->sizes() == want && v_new->sizes() == want && same(*k_new) && same(*v_new),
-                "attn decode: k_new and v_new must be [B, Sq, Hkv, D] = ", want,
+                who, ": k_new and v_new must be [B, Sq, Hkv, D] = ", want,
                 " of q's dtype and device, got ", k_new->sizes(), " and ", v_new->sizes());
   }
   TORCH_CHECK(Smax < (int64_t{1} << 24) && Sq < (int64_t{1} << 24),
-              "attn decode: Smax and Sq must be below 2^24");
+              who, ": Smax and Sq must be below 2^24");
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
+  P.scale = (float)scale;
+  P.dtype = dtype_of(q);
+  return P;
+}
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cache,
+                                                  at::Tensor v_cache, at::Tensor cache_seqlens,
+                                                  c10::optional<at::Tensor> k_new,
+                                                  c10::optional<at::Tensor> v_new, double scale,
+                                                  int64_t num_splits) {
+  c10::NoGradGuard no_grad_;
+  AttnDecode P = cache_problem("attn decode", q, k_cache, v_cache, cache_seqlens, k_new, v_new,
+                               scale);
+  const int64_t B = P.B, Sq = P.Sq, H = P.H, D = P.D, Hkv = P.Hkv;
   const int64_t R = H / Hkv * Sq;
   TORCH_CHECK(B * Hkv <= 65535 && (R + 31) / 32 <= 65535,
               "attn decode: batch x key/value heads = ", B * Hkv, " or rows per group = ", R,
@@ -466,10 +484,6 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cac
   TORCH_CHECK(num_splits >= 0 && num_splits <= kAttnDecodeMaxSplits,
               "attn decode: num_splits must be in [1, ", kAttnDecodeMaxSplits, "], got ",
               num_splits);
-  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
-  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
-  P.scale = (float)scale;
-  P.dtype = dtype_of(q);
   at::Tensor o = at::empty({B, Sq, H, D}, q.options());
   at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
   if (B == 0 || Sq == 0) return {o, lse};
@@ -487,6 +501,26 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cac
     P.lse_part = lse_part.data_ptr<float>();
   }
   attn_decode(P, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_prefill_op(at::Tensor q, at::Tensor k_cache,
+                                                   at::Tensor v_cache, at::Tensor cache_seqlens,
+                                                   c10::optional<at::Tensor> k_new,
+                                                   c10::optional<at::Tensor> v_new, double scale) {
+  c10::NoGradGuard no_grad_;
+  AttnPrefill P;
+  P.d = cache_problem("attn prefill", q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale);
+  const int64_t B = P.d.B, Sq = P.d.Sq, H = P.d.H, D = P.d.D, Hkv = P.d.Hkv;
+  const int64_t tiles = (H / Hkv * Sq + 127) / 128;  // 128 rows of a key/value head's group each
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && tiles <= (int64_t{1} << 23) &&
+                  tiles * Hkv * B < (int64_t{1} << 31),
+              "attn prefill: batch ", B, ", ", Hkv, " key/value heads or their product with the ",
+              tiles, " row tiles exceeds a launch grid");
+  at::Tensor o = at::empty({B, Sq, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (B == 0 || Sq == 0) return {o, lse};
+  attn_prefill(P, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
   return {o, lse};
 }
 

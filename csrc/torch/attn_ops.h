@@ -93,6 +93,15 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_op(at::Tensor q, at::Tensor k_cac
                                                   c10::optional<at::Tensor> v_new, double scale,
                                                   int64_t num_splits);
 
+// Sq new tokens (any Sq: a prompt chunk, a turn, a draft) over a contiguous 16-bit KV cache that
+// holds a prefix (csrc/hip/attention_prefill.hip; forward only, no gradient).  Tensors, lengths,
+// mask, append and results are attn_decode_op's word for word; the kernels split the rows, not
+// the keys: one launch, no workspace, no num_splits, bitwise reproducible.
+std::tuple<at::Tensor, at::Tensor> attn_prefill_op(at::Tensor q, at::Tensor k_cache,
+                                                   at::Tensor v_cache, at::Tensor cache_seqlens,
+                                                   c10::optional<at::Tensor> k_new,
+                                                   c10::optional<at::Tensor> v_new, double scale);
+
 // The same step over a paged KV cache (csrc/hip/attention_decode_paged.hip).  k_pages, v_pages:
 // [num_pages, P, Hkv, D] views (any page / row / head strides, head dim contiguous, 16-B
 // aligned rows, P in {16, 32, 64, 128, 256}, P x row stride below 2^32 bytes); block_table:

@@ -128,6 +128,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   attn.def("decode", &attn_decode_op, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
            py::arg("cache_seqlens"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(),
            py::arg("scale") = 1.0, py::arg("num_splits") = 0);
+  attn.def("prefill", &attn_prefill_op, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+           py::arg("cache_seqlens"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(),
+           py::arg("scale") = 1.0);
   attn.def("decode_paged", &attn_decode_paged_op, py::arg("q"), py::arg("k_pages"),
            py::arg("v_pages"), py::arg("block_table"), py::arg("cache_seqlens"),
            py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("scale") = 1.0,

@@ -12,6 +12,7 @@
     python tools/microbench.py attn-decode  # decode step over a KV cache vs SDPA, the byte floor
     python tools/microbench.py attn-decode-paged  # ... over a paged cache vs the contiguous one
     python tools/microbench.py attn-decode-fp8  # ... over an FP8 cache vs the 16-bit one
+    python tools/microbench.py attn-prefill  # Sq new tokens behind a cached prefix vs decode, SDPA
 """
 from __future__ import annotations
 
@@ -1244,11 +1245,83 @@ def bench_conv1x1_stats(args):
             n, ci, co, hw, mb, bw(t_g), t_gs, bw(t_o), t_os), flush=True)
 
 
+def bench_attn_prefill(args):
+    """Sq new tokens behind a prefix of P cached tokens (csrc/hip/attention_prefill.hip): bf16,
+    every batch element at L = P + Sq keys in a cache of Smax = L rows, no append, through the
+    public op, against fused_attention_decode on the same call (what served it before), against
+    SDPA with enable_gqa=True under the bottom-right mask and, at P = 0, against
+    fused_attention(causal=True) on the same tensors.  The timing method of bench_attn_decode:
+    the variants alternate in one process over ROUNDS rounds after a warm-up, each timed window
+    ends in a device synchronise (timeit); a variant's iterations per window come from one
+    probe call so that a window lasts about 30 ms (5 to 100 iterations).  Prints medians, the
+    spread (max - min) / median and the ratios to the new op (above 1: the new op is faster)."""
+    from apex_example_amd.ops import (fused_attention, fused_attention_decode,
+                                      fused_attention_prefill)
+
+    dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
+    print("| shape (B x H / Hkv, D, Sq, prefix) | workgroups | prefill us | spread | decode us | "
+          "spread | decode / prefill | sdpa us | sdpa / prefill | causal fwd us | "
+          "causal / prefill |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    shapes = [(b, 16, hkv, d, sq, pre) for d in (64, 128) for hkv in (16, 2) for b in (1, 8)
+              for sq in (128, 512, 2048) for pre in (0, 2048, 8192)]
+    for b, h, hkv, d, sq, pre in shapes:
+        L = pre + sq
+        q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+        kv = torch.randn(b, L, 2, hkv, d, device=dev, dtype=dt)
+        lens = torch.full((b,), L, dtype=torch.int32, device=dev)
+        sq_, sk, sv = q.transpose(1, 2), kv[:, :, 0].transpose(1, 2), kv[:, :, 1].transpose(1, 2)
+        keep = torch.ones(sq, L, dtype=torch.bool, device=dev).tril(pre)
+
+        def prefill():
+            fused_attention_prefill(q, kv[:, :, 0], kv[:, :, 1], lens)
+
+        def decode():
+            fused_attention_decode(q, kv[:, :, 0], kv[:, :, 1], lens)
+
+        def sdpa():
+            F.scaled_dot_product_attention(sq_, sk, sv, attn_mask=keep, enable_gqa=True)
+
+        def causal():
+            fused_attention(q, kv[:, :, 0], kv[:, :, 1], causal=True)
+
+        variants = [("prefill", prefill), ("decode", decode), ("sdpa", sdpa)]
+        if pre == 0:
+            variants.append(("causal", causal))
+        t_end = time.time() + 0.5  # clock / first-use ramp, as in bench_attn
+        while time.time() < t_end:
+            prefill()
+            torch.cuda.synchronize()
+        times, iters = {}, {}
+        with torch.no_grad():
+            for n, fn in variants:
+                try:
+                    iters[n] = int(min(100, max(5, 30e3 / timeit(fn, iters=2, warmup=2))))
+                    times[n] = []
+                except Exception as e:  # noqa: BLE001
+                    print("%s failed: %s" % (n, str(e)[:200]))
+            for _ in range(ROUNDS):
+                for n, fn in variants:
+                    if n in times:
+                        times[n].append(timeit(fn, iters=iters[n], warmup=2))
+        med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
+        spread = lambda xs: 100 * (max(xs) - min(xs)) / med(xs)  # noqa: E731
+        tp = med(times["prefill"])
+        vs = lambda n: ("%.1f | %.2f x" % (med(times[n]), med(times[n]) / tp)  # noqa: E731
+                        if n in times else "- | -")
+        print("| %d x %d / %d, %d, %d, %d | %d | %.1f | %.1f %% | %.1f | %.1f %% | %.2f x | %s | "
+              "%s |" % (b, h, hkv, d, sq, pre, (h // hkv * sq + 127) // 128 * hkv * b, tp,
+                        spread(times["prefill"]), med(times["decode"]), spread(times["decode"]),
+                        med(times["decode"]) / tp, vs("sdpa"), vs("causal")), flush=True)
+        del q, kv, keep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["bn", "bn-tune", "conv1x1", "conv1x1-own", "conv1x1-stats", "wgrad", "wgrad-o1", "wgrad-dense", "conv3x3", "conv-s2", "optim", "ln", "ln-join", "conv-bnbwd", "lamb",
                              "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa",
-                             "attn-decode", "attn-decode-paged", "attn-decode-fp8"])
+                             "attn-decode", "attn-decode-paged", "attn-decode-fp8",
+                             "attn-prefill"])
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
@@ -1257,7 +1330,8 @@ def main():
      "attn-pairmask": bench_attn_pairmask, "attn-gqa": bench_attn_gqa,
      "attn-decode": bench_attn_decode,
      "attn-decode-paged": bench_attn_decode_paged,
-     "attn-decode-fp8": bench_attn_decode_fp8}[a.what](a)
+     "attn-decode-fp8": bench_attn_decode_fp8,
+     "attn-prefill": bench_attn_prefill}[a.what](a)
 
 
 if __name__ == "__main__":
