@@ -7,7 +7,8 @@ split-KV decode kernels (``fused_attention_decode``), later chunks of a prompt f
 (``prefill_chunk``) through the chunked-prefill kernels (``fused_attention_prefill``); with
 ``page_size`` the cache is a
 ``PagedKVCache``, a page pool and a block table read by the paged decode kernels; with
-``kv_dtype=torch.float8_e4m3fn`` the ``KVCache`` holds FP8 rows and one fp32 scale per row.
+``kv_dtype=torch.float8_e4m3fn`` the ``KVCache`` holds FP8 rows and one fp32 scale per row, read
+by the FP8 variants of the decode and chunked-prefill kernels.
 
 gpt2_medium(): 24 layers, d_model 1024, 16 heads, vocab 50257, 1024 positions
 = 354,823,168 parameters in 292 tensors.
@@ -50,11 +51,13 @@ class GPT2Config:
     fused_residual_ln: bool = True
 
 
-# New rows (tokens x query heads of a group) from which a chunk behind a filled contiguous 16-bit
-# cache goes to the chunked-prefill kernels instead of the decode kernels: the smallest measured
-# row count at which they beat decode at every measured cache length (docs/PERF.md, "Attention:
+# New rows (tokens x query heads of a group) from which a chunk behind a filled contiguous cache
+# goes to the chunked-prefill kernels instead of the decode kernels: the smallest measured row
+# count at which they beat decode at every measured cache length (docs/PERF.md, "Attention:
 # chunked prefill over a KV cache": below it decode's split-KV wins at batch 1; the section also
-# names the small grids above it where decode is still faster).
+# names the small grids above it where decode is still faster).  The FP8 cache's own table gives
+# the same 2048 by the same rule ("Attention: chunked prefill over an FP8 KV cache"), so one
+# constant serves both cache dtypes.
 PREFILL_MIN_ROWS = 2048
 
 
@@ -190,12 +193,14 @@ class GPT2Attention(nn.Module):
         ``KVCache`` or ``PagedKVCache``, storing their keys and values (the model advances the
         lengths).  An empty cache is a prefill on the causal kernels (a paged one stores the
         prompt's rows through ``paged_kv_append``); a filled one a decode step, which appends in
-        its own launch - or, for a contiguous 16-bit cache and s * (h / hkv) >= PREFILL_MIN_ROWS
-        new rows, a chunk on the chunked-prefill kernels, which append the same way.  Off the
-        GPU / in fp32: SDPA over the filled rows (a paged cache's gathered through the table).
-        An FP8 cache: the new rows are quantised on their way in (``fp8_kv_append`` or the decode call's own append; off the kernels by their torch
-        mirror ``fp8_quantize_rows``), a decode step attends the quantised rows, its own
-        included, and a prefill the prompt's own 16-bit keys and values, on either path."""
+        its own launch - or, for a contiguous cache (16-bit or FP8) and s * (h / hkv) >=
+        PREFILL_MIN_ROWS new rows, a chunk on the chunked-prefill kernels, which append the same
+        way.  Off the GPU / in fp32: SDPA over the filled rows (a paged cache's gathered through
+        the table).  An FP8 cache: the new rows are quantised on their way in (``fp8_kv_append``
+        or the decode / chunked-prefill call's own append; off the kernels by their torch mirror
+        ``fp8_quantize_rows``), a decode step or a chunk behind a filled cache attends the
+        quantised rows, its own included, and a prefill into an empty cache the prompt's own
+        16-bit keys and values, on either path."""
         b, s, e = x.shape
         h, hkv, d = self.h, self.hkv or self.h, self.d
         y = self._lin(self.c_attn, x)
@@ -211,9 +216,11 @@ class GPT2Attention(nn.Module):
         paged = isinstance(cache, PagedKVCache)  # kv: [num_pages, P, 2, Hkv, D] behind a table
         fused = self.fused and fused_attn.supported(q, d)
         sc = cache.scales[self.layer_idx] if cache.kv_dtype is not None else None
-        if fused and L > 0 and not paged and sc is None and s * (h // hkv) >= PREFILL_MIN_ROWS:
+        if fused and L > 0 and not paged and s * (h // hkv) >= PREFILL_MIN_ROWS:
             return fused_attn.fused_attention_prefill(
-                q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v).view(b, s, e)
+                q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v,
+                k_scale=None if sc is None else sc[:, 0],
+                v_scale=None if sc is None else sc[:, 1]).view(b, s, e)
         if fused and L > 0:
             return fused_attn.fused_attention_decode(
                 q, kv[:, :, 0], kv[:, :, 1], cache.lengths, k_new=k, v_new=v,

@@ -104,7 +104,12 @@ of a key/value head's group in token order, 128 per workgroup, every 64-key K / 
 four waves through LDS, each workgroup's key loop ending at the last key its tokens see.  One
 launch, no ``num_splits``, bitwise reproducible.  It wins where the row tiles fill the device
 and loses to decode's split-KV where they do not (B = 1 with a few hundred rows): docs/PERF.md,
-"Attention: chunked prefill over a KV cache".  Paged and FP8 caches are refused here.
+"Attention: chunked prefill over a KV cache".  With float8_e4m3fn caches and ``k_scale`` /
+``v_scale`` the same call runs the FP8 variant of those kernels (csrc/hip/
+attention_prefill_fp8.hip): the row split and causal skipping above over shared 64-key byte
+tiles (half the LDS), the bytes converted in registers and the scales applied as in FP8 decode,
+the new rows quantised by the same append; docs/PERF.md, "Attention: chunked prefill over an FP8
+KV cache".  Paged caches are refused here, 16-bit or FP8.
 
 Eligibility (``supported``): GPU tensor, bf16/fp16, head dim 64 or 128, q and k / v of one
 batch size (the query and key lengths may differ) and H query heads over Hkv key/value heads
@@ -697,7 +702,7 @@ def _check_fp8(first, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_t
         raise ValueError("an 8-bit KV cache is float8_e4m3fn in both halves, got %s and %s" % (
             k_cache.dtype, v_cache.dtype))
     if t0.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError("decode takes bf16 / fp16 %s, got %s" % (name0, t0.dtype))
+        raise ValueError("an FP8 KV cache takes bf16 / fp16 %s, got %s" % (name0, t0.dtype))
     B, D = t0.size(0), t0.size(3)
     if D not in HEAD_DIMS:
         raise ValueError("head dim must be one of %s, got %d" % (HEAD_DIMS, D))
@@ -723,8 +728,10 @@ def _check_fp8(first, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_t
         raise ValueError("cache_seqlens must be contiguous: the kernels read the tensor itself")
 
 
-def _decode_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, num_splits,
-                return_lse, block_table, k_scale, v_scale):
+def _check_fp8_call(what, q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, block_table,
+                    k_scale, v_scale):
+    """The tensors of a call over an FP8 KV cache (``what``: "decode" or "prefill"), ValueError
+    on anything refused; -> the softmax scale."""
     if (k_new is None) != (v_new is None):
         raise ValueError("k_new and v_new come as a pair")
     _check_fp8(("q", q), k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table)
@@ -735,14 +742,29 @@ def _decode_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, num_spl
         _check_new_rows(k_new, v_new, q, (B, Sq, k_cache.size(2), D))
         named += [k_new, v_new]
     if torch.is_grad_enabled() and any(t.requires_grad for t in named):
-        raise ValueError("fused_attention_decode is forward only: call it under torch.no_grad() "
-                         "or on detached tensors")
+        raise ValueError("fused_attention_%s is forward only: call it under torch.no_grad() "
+                         "or on detached tensors" % what)
+    return 1.0 / math.sqrt(D) if scale is None else scale
+
+
+def _decode_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, num_splits,
+                return_lse, block_table, k_scale, v_scale):
+    scale = _check_fp8_call("decode", q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
+                            block_table, k_scale, v_scale)
     cap = _C().DECODE_MAX_SPLITS
     if num_splits is not None and not 1 <= int(num_splits) <= cap:
         raise ValueError("num_splits must be in [1, %d], got %s" % (cap, num_splits))
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
     o, lse = _C().decode_fp8(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, k_new, v_new,
                              float(scale), 0 if num_splits is None else int(num_splits))
+    return (o, lse) if return_lse else o
+
+
+def _prefill_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, return_lse,
+                 block_table, k_scale, v_scale):
+    scale = _check_fp8_call("prefill", q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale,
+                            block_table, k_scale, v_scale)
+    o, lse = _C().prefill_fp8(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, k_new, v_new,
+                              float(scale))
     return (o, lse) if return_lse else o
 
 
@@ -854,7 +876,7 @@ def fused_attention_prefill(q, k_cache, v_cache, cache_seqlens, k_new=None, v_ne
                             scale=None, return_lse=False, block_table=None, k_scale=None,
                             v_scale=None):
     """Sq new tokens (a prompt chunk, the next turn, a draft: any Sq >= 1) over a contiguous
-    bf16 / fp16 KV cache that holds a prefix.  Every tensor and every contract is
+    KV cache that holds a prefix.  Every tensor and every contract is
     ``fused_attention_decode``'s: q [B, Sq, H, D]; k_cache, v_cache [B, Smax, Hkv, D] views;
     cache_seqlens int32 [B] on the GPU, read by the kernels only; with k_new and v_new [B, Sq,
     Hkv, D] the rows are first stored at rows cache_seqlens[b] + i and L_b = cache_seqlens[b] +
@@ -862,13 +884,19 @@ def fused_attention_prefill(q, k_cache, v_cache, cache_seqlens, k_new=None, v_ne
     Sq + i, a query that sees no key gets o = 0 and lse = -inf; cache_seqlens is not advanced.
     -> o [B, Sq, H, D] contiguous and, with return_lse, the fp32 [B, H, Sq] lse in log2 units.
     One launch without a workspace: there is no num_splits and results are bitwise
-    reproducible.  Forward only.  ValueError for an 8-bit cache (or scales) and for a
-    block_table: this op serves the contiguous 16-bit cache only, those go to
-    ``fused_attention_decode``."""
+    reproducible.  Forward only.
+
+    k_scale, v_scale: with float8_e4m3fn k_cache and v_cache (both), the fp32 [B, Hkv, Smax]
+    per-row scales of ``fused_attention_decode``, whose FP8 contract holds word for word: q,
+    k_new and v_new stay bf16 / fp16, k_new / v_new are quantised per row on their way in
+    (``fp8_quantize_rows``) and the chunk attends the quantised rows, its own included.
+    ValueError without the scales or with one of them, with scales on a 16-bit cache, with
+    caches of two dtypes or another 8-bit dtype, and for a block_table with either cache dtype:
+    a paged cache goes to ``fused_attention_decode``."""
     if k_scale is not None or v_scale is not None or any(
             isinstance(t, torch.Tensor) and t.dtype.itemsize == 1 for t in (k_cache, v_cache)):
-        raise ValueError("fused_attention_prefill takes a bf16 / fp16 KV cache: an 8-bit cache "
-                         "(k_scale / v_scale) is served by fused_attention_decode only")
+        return _prefill_fp8(q, k_cache, v_cache, cache_seqlens, k_new, v_new, scale, return_lse,
+                            block_table, k_scale, v_scale)
     if block_table is not None:
         raise ValueError("fused_attention_prefill takes a contiguous KV cache: a paged one "
                          "(block_table) is served by fused_attention_decode only")

@@ -88,46 +88,6 @@ __device__ __forceinline__ int fp8_len(const int* lens, int b, int append, int S
   return l > Smax ? Smax : l;
 }
 
-// LDS DMA of 4 bytes per lane into M0 + 4 * lane (glds16o's form: wave-uniform base, per-lane
-// 32-bit byte offset)
-__device__ __forceinline__ void glds4o(const void* base, uint32_t off, unsigned char* l) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("global_load_lds_dword %0, %1" : : "v"(off), "s"(base), "{m0}"(lds_addr32(l))
-               : "memory");
-#endif
-}
-
-// byte offset of 16-byte chunk c of key r in a [KS][D bytes] image (header: K, V)
-template <int D>
-__device__ __forceinline__ int swz_k8(int r, int c) {
-  return r * D + ((c ^ (D == 64 ? (r >> 2) & 3 : (r >> 1) & 7)) << 4);
-}
-template <int D>
-__device__ __forceinline__ int swz_v8(int r, int c) {
-  const int x = D == 64 ? ((r >> 3) & 1) << 1 : (((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2);
-  return r * D + ((c ^ x) << 4);
-}
-
-// 8 e4m3 bytes (lo: elements 0 .. 3, hi: 4 .. 7) as a 16-bit MFMA fragment, exact
-template <typename T>
-__device__ __forceinline__ typename Frag<T>::v8 fp8_frag(uint32_t lo, uint32_t hi) {
-  uint32_t w[4];
-  if constexpr (std::is_same<T, bf16_t>::value) {
-    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.f, false));
-    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.f, true));
-    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.f, false));
-    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.f, true));
-  } else {
-    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.f, false));
-    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.f, true));
-    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.f, false));
-    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.f, true));
-  }
-  return __builtin_bit_cast(typename Frag<T>::v8, *reinterpret_cast<uint4*>(w));
-}
-
-typedef int v2i_t __attribute__((ext_vector_type(2)));
-
 template <typename T, int D>
 __global__ void __launch_bounds__(kAT) attn_decode_fp8_k(Fp8Args a) {
   typedef typename Frag<T>::v8 v8;

@@ -650,6 +650,12 @@ struct AttnPrefill {
 };
 // o [B][Sq][H][D] contiguous, lse [B][H][Sq] (log2 units)
 void attn_prefill(const AttnPrefill& p, void* o, float* lse, hipStream_t st);
+// The same chunk over an FP8 KV cache (attention_prefill_fp8.hip): attn_prefill's row split,
+// causal bounds, launch limits (it aborts beyond them) and single launch over AttnDecodeFp8's
+// caches and scales; d.k_new / d.v_new go through attn_fp8_append first, so the chunk attends
+// the quantised rows, its own included.  d.nsplit, d.o_part and d.lse_part are not read.
+// Bitwise reproducible.
+void attn_prefill_fp8(const AttnDecodeFp8& p, void* o, float* lse, hipStream_t st);
 
 // ---- fused softmax cross entropy with label smoothing (xentropy.hip) ---------
 // x [rows, V] row-major (T = fp32/fp16/bf16); loss [rows] (TO), lse [rows] fp32

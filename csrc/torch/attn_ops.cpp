@@ -697,6 +697,48 @@ int64_t fp8_views(AttnDecodeFp8& P, const at::Tensor& k_cache, const at::Tensor&
   P.v_scale = v_scale.data_ptr<float>(); P.vs_sb = v_scale.stride(0); P.vs_sh = v_scale.stride(1);
   return Smax;
 }
+// cache_problem for an FP8 cache (attn_decode_fp8_op, attn_prefill_fp8_op): 16-bit q and new
+// rows, the caches and scales through fp8_views, the lengths tensor, paired new rows.
+AttnDecodeFp8 fp8_cache_problem(const char* who, const at::Tensor& q, const at::Tensor& k_cache,
+                                const at::Tensor& v_cache, const at::Tensor& k_scale,
+                                const at::Tensor& v_scale, const at::Tensor& cache_seqlens,
+                                const c10::optional<at::Tensor>& k_new,
+                                const c10::optional<at::Tensor>& v_new, double scale) {
+  AttnDecodeFp8 PP;
+  AttnDecode& P = PP.d;
+  P.q = view_of(q, "q");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf,
+              who, ": q must be bf16 or fp16");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) > 0 && H % k_cache.size(2) == 0,
+              who, ": the heads do not split: q ", q.sizes(), ", k_cache ", k_cache.sizes());
+  const int64_t Hkv = k_cache.size(2);
+  const int64_t Smax = fp8_views(PP, k_cache, v_cache, k_scale, v_scale, q, B, Hkv, D, who);
+  auto same = [&](const at::Tensor& t) {
+    return t.scalar_type() == q.scalar_type() && t.device() == q.device();
+  };
+  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == q.device() &&
+                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
+                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
+              who, ": cache_seqlens must be a contiguous int32 [B] tensor on q's device, got ",
+              cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
+  TORCH_CHECK(k_new.has_value() == v_new.has_value(), who, ": k_new and v_new come as a pair");
+  if (k_new.has_value()) {
+    P.k_new = view_of(*k_new, "k_new");
+    P.v_new = view_of(*v_new, "v_new");
+    const std::vector<int64_t> dims{B, Sq, Hkv, D};
+    const at::IntArrayRef want(dims);
+    TORCH_CHECK(k_new->sizes() == want && v_new->sizes() == want && same(*k_new) && same(*v_new),
+                who, ": k_new and v_new must be [B, Sq, Hkv, D] = ", want,
+                " of q's dtype and device, got ", k_new->sizes(), " and ", v_new->sizes());
+  }
+  TORCH_CHECK(Sq < (int64_t{1} << 24), who, ": Sq must be below 2^24");
+  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
+  P.scale = (float)scale;
+  P.dtype = dtype_of(q);
+  return PP;
+}
 }  // namespace
 
 std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
@@ -704,38 +746,10 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
     at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
     double scale, int64_t num_splits) {
   c10::NoGradGuard no_grad_;
-  AttnDecodeFp8 PP;
+  AttnDecodeFp8 PP = fp8_cache_problem("attn decode fp8", q, k_cache, v_cache, k_scale, v_scale,
+                                       cache_seqlens, k_new, v_new, scale);
   AttnDecode& P = PP.d;
-  P.q = view_of(q, "q");
-  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16 || q.scalar_type() == at::kHalf,
-              "attn decode fp8: q must be bf16 or fp16");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) > 0 && H % k_cache.size(2) == 0,
-              "attn decode fp8: the heads do not split: q ", q.sizes(), ", k_cache ",
-              k_cache.sizes());
-  const int64_t Hkv = k_cache.size(2);
-  const int64_t Smax = fp8_views(PP, k_cache, v_cache, k_scale, v_scale, q, B, Hkv, D,
-                                 "attn decode fp8");
-  auto same = [&](const at::Tensor& t) {
-    return t.scalar_type() == q.scalar_type() && t.device() == q.device();
-  };
-  TORCH_CHECK(cache_seqlens.is_cuda() && cache_seqlens.device() == q.device() &&
-                  cache_seqlens.scalar_type() == at::kInt && cache_seqlens.dim() == 1 &&
-                  cache_seqlens.size(0) == B && cache_seqlens.is_contiguous(),
-              "attn decode fp8: cache_seqlens must be a contiguous int32 [B] tensor on q's "
-              "device, got ", cache_seqlens.scalar_type(), " ", cache_seqlens.sizes());
-  TORCH_CHECK(k_new.has_value() == v_new.has_value(),
-              "attn decode fp8: k_new and v_new come as a pair");
-  if (k_new.has_value()) {
-    P.k_new = view_of(*k_new, "k_new");
-    P.v_new = view_of(*v_new, "v_new");
-    const std::vector<int64_t> dims{B, Sq, Hkv, D};
-    const at::IntArrayRef want(dims);
-    TORCH_CHECK(k_new->sizes() == want && v_new->sizes() == want && same(*k_new) && same(*v_new),
-                "attn decode fp8: k_new and v_new must be [B, Sq, Hkv, D] = ", want,
-                " of q's dtype and device, got ", k_new->sizes(), " and ", v_new->sizes());
-  }
-  TORCH_CHECK(Sq < (int64_t{1} << 24), "attn decode fp8: Sq must be below 2^24");
+  const int64_t B = P.B, Sq = P.Sq, H = P.H, D = P.D, Hkv = P.Hkv;
   const int64_t R = H / Hkv * Sq;
   TORCH_CHECK(B * Hkv <= 65535 && (R + 31) / 32 <= 65535,
               "attn decode fp8: batch x key/value heads = ", B * Hkv, " or rows per group = ", R,
@@ -743,10 +757,6 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
   TORCH_CHECK(num_splits >= 0 && num_splits <= kAttnDecodeMaxSplits,
               "attn decode fp8: num_splits must be in [1, ", kAttnDecodeMaxSplits, "], got ",
               num_splits);
-  P.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
-  P.D = (int)D; P.B = (int)B; P.H = (int)H; P.Hkv = (int)Hkv; P.Sq = (int)Sq; P.Smax = (int)Smax;
-  P.scale = (float)scale;
-  P.dtype = dtype_of(q);
   at::Tensor o = at::empty({B, Sq, H, D}, q.options());
   at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
   if (B == 0 || Sq == 0) return {o, lse};
@@ -764,6 +774,26 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
     P.lse_part = lse_part.data_ptr<float>();
   }
   attn_decode_fp8(PP, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_prefill_fp8_op(
+    at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale,
+    at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+    double scale) {
+  c10::NoGradGuard no_grad_;
+  const AttnDecodeFp8 PP = fp8_cache_problem("attn prefill fp8", q, k_cache, v_cache, k_scale,
+                                             v_scale, cache_seqlens, k_new, v_new, scale);
+  const int64_t B = PP.d.B, Sq = PP.d.Sq, H = PP.d.H, D = PP.d.D, Hkv = PP.d.Hkv;
+  const int64_t tiles = (H / Hkv * Sq + 127) / 128;  // 128 rows of a key/value head's group each
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535 && tiles <= (int64_t{1} << 23) &&
+                  tiles * Hkv * B < (int64_t{1} << 31),
+              "attn prefill fp8: batch ", B, ", ", Hkv, " key/value heads or their product with "
+              "the ", tiles, " row tiles exceeds a launch grid");
+  at::Tensor o = at::empty({B, Sq, H, D}, q.options());
+  at::Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (B == 0 || Sq == 0) return {o, lse};
+  attn_prefill_fp8(PP, o.data_ptr(), lse.data_ptr<float>(), cur_stream());
   return {o, lse};
 }
 

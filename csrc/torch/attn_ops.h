@@ -130,6 +130,14 @@ std::tuple<at::Tensor, at::Tensor> attn_decode_fp8_op(
     at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
     double scale, int64_t num_splits);
 
+// Sq new tokens over the same FP8 KV cache on the row-split kernels (csrc/hip/
+// attention_prefill_fp8.hip): attn_decode_fp8_op's tensors and append, attn_prefill_op's single
+// launch without num_splits, bitwise reproducible.
+std::tuple<at::Tensor, at::Tensor> attn_prefill_fp8_op(
+    at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, at::Tensor k_scale, at::Tensor v_scale,
+    at::Tensor cache_seqlens, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+    double scale);
+
 // The quantising append alone: k_new / v_new [B, Sn, Hkv, D] (bf16 / fp16, any Sn) into cache
 // rows cache_seqlens[b] + i and their scales; rows outside [0, Smax) are skipped.  One launch,
 // no host sync.

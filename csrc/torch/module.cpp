@@ -142,6 +142,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cache_seqlens"),
            py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("scale") = 1.0,
            py::arg("num_splits") = 0);
+  attn.def("prefill_fp8", &attn_prefill_fp8_op, py::arg("q"), py::arg("k_cache"),
+           py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"), py::arg("cache_seqlens"),
+           py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("scale") = 1.0);
   attn.def("fp8_append", &attn_fp8_append_op, py::arg("k_new"), py::arg("v_new"),
            py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"), py::arg("v_scale"),
            py::arg("cache_seqlens"));

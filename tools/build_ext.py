@@ -38,7 +38,7 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA = {"attention_d128.hip": _NO_PK_F32, "attention_pairmask.hip": _NO_PK_F32,
              "attention_gqa.hip": _NO_PK_F32, "attention_decode.hip": _NO_PK_F32,
              "attention_decode_paged.hip": _NO_PK_F32, "attention_decode_fp8.hip": _NO_PK_F32,
-             "attention_prefill.hip": _NO_PK_F32}
+             "attention_prefill.hip": _NO_PK_F32, "attention_prefill_fp8.hip": _NO_PK_F32}
 # Sources that include another source: attention_pairmask.hip instantiates the head dim 64
 # kernel templates of attention.hip under its own flags, attention_gqa.hip those of both
 # head dims.

@@ -13,6 +13,7 @@
     python tools/microbench.py attn-decode-paged  # ... over a paged cache vs the contiguous one
     python tools/microbench.py attn-decode-fp8  # ... over an FP8 cache vs the 16-bit one
     python tools/microbench.py attn-prefill  # Sq new tokens behind a cached prefix vs decode, SDPA
+    python tools/microbench.py attn-prefill --fp8  # ... over an FP8 cache vs FP8 decode, 16-bit
 """
 from __future__ import annotations
 
@@ -1254,15 +1255,26 @@ def bench_attn_prefill(args):
     the variants alternate in one process over ROUNDS rounds after a warm-up, each timed window
     ends in a device synchronise (timeit); a variant's iterations per window come from one
     probe call so that a window lasts about 30 ms (5 to 100 iterations).  Prints medians, the
-    spread (max - min) / median and the ratios to the new op (above 1: the new op is faster)."""
-    from apex_example_amd.ops import (fused_attention, fused_attention_decode,
+    spread (max - min) / median and the ratios to the new op (above 1: the new op is faster).
+
+    --fp8 (csrc/hip/attention_prefill_fp8.hip): the same shapes, alternation, rounds and
+    windows with the cache quantised from the same keys by fp8_kv_append: the FP8 prefill op
+    against fused_attention_decode on the same FP8 call (what served it before) and against the
+    16-bit prefill op on the 16-bit keys."""
+    from apex_example_amd.ops import (fp8_kv_append, fused_attention, fused_attention_decode,
                                       fused_attention_prefill)
 
     dev, dt, ROUNDS = "cuda", torch.bfloat16, 5
-    print("| shape (B x H / Hkv, D, Sq, prefix) | workgroups | prefill us | spread | decode us | "
-          "spread | decode / prefill | sdpa us | sdpa / prefill | causal fwd us | "
-          "causal / prefill |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    if args.fp8:
+        print("| shape (B x H / Hkv, D, Sq, prefix) | workgroups | fp8 prefill us | spread | "
+              "fp8 decode us | spread | fp8 decode / fp8 prefill | 16-bit prefill us | spread | "
+              "16-bit prefill / fp8 prefill |")
+        print("|---|---|---|---|---|---|---|---|---|---|")
+    else:
+        print("| shape (B x H / Hkv, D, Sq, prefix) | workgroups | prefill us | spread | "
+              "decode us | spread | decode / prefill | sdpa us | sdpa / prefill | "
+              "causal fwd us | causal / prefill |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|")
     shapes = [(b, 16, hkv, d, sq, pre) for d in (64, 128) for hkv in (16, 2) for b in (1, 8)
               for sq in (128, 512, 2048) for pre in (0, 2048, 8192)]
     for b, h, hkv, d, sq, pre in shapes:
@@ -1288,6 +1300,19 @@ def bench_attn_prefill(args):
         variants = [("prefill", prefill), ("decode", decode), ("sdpa", sdpa)]
         if pre == 0:
             variants.append(("causal", causal))
+        if args.fp8:
+            kv8 = torch.empty(b, L, 2, hkv, d, device=dev, dtype=torch.float8_e4m3fn)
+            sc = torch.empty(b, 2, hkv, L, device=dev, dtype=torch.float32)
+            fp8_kv_append(kv[:, :, 0], kv[:, :, 1], kv8[:, :, 0], kv8[:, :, 1], sc[:, 0],
+                          sc[:, 1], torch.zeros_like(lens))
+            fp8 = dict(k_scale=sc[:, 0], v_scale=sc[:, 1])
+            variants = [
+                ("prefill", lambda: fused_attention_prefill(q, kv8[:, :, 0], kv8[:, :, 1], lens,
+                                                            **fp8)),
+                ("decode", lambda: fused_attention_decode(q, kv8[:, :, 0], kv8[:, :, 1], lens,
+                                                          **fp8)),
+                ("wide", prefill)]
+            prefill = variants[0][1]  # the warm-up below runs the op under test
         t_end = time.time() + 0.5  # clock / first-use ramp, as in bench_attn
         while time.time() < t_end:
             prefill()
@@ -1307,6 +1332,15 @@ def bench_attn_prefill(args):
         med = lambda xs: sorted(xs)[len(xs) // 2]  # noqa: E731
         spread = lambda xs: 100 * (max(xs) - min(xs)) / med(xs)  # noqa: E731
         tp = med(times["prefill"])
+        if args.fp8:
+            print("| %d x %d / %d, %d, %d, %d | %d | %.1f | %.1f %% | %.1f | %.1f %% | %.2f x | "
+                  "%.1f | %.1f %% | %.2f x |" % (
+                      b, h, hkv, d, sq, pre, (h // hkv * sq + 127) // 128 * hkv * b, tp,
+                      spread(times["prefill"]), med(times["decode"]), spread(times["decode"]),
+                      med(times["decode"]) / tp, med(times["wide"]), spread(times["wide"]),
+                      med(times["wide"]) / tp), flush=True)
+            del q, kv, keep, kv8, sc
+            continue
         vs = lambda n: ("%.1f | %.2f x" % (med(times[n]), med(times[n]) / tp)  # noqa: E731
                         if n in times else "- | -")
         print("| %d x %d / %d, %d, %d, %d | %d | %.1f | %.1f %% | %.1f | %.1f %% | %.2f x | %s | "
@@ -1322,6 +1356,8 @@ def main():
                              "attn", "attn-packed", "attn-d128", "attn-pairmask", "attn-gqa",
                              "attn-decode", "attn-decode-paged", "attn-decode-fp8",
                              "attn-prefill"])
+    ap.add_argument("--fp8", action="store_true",
+                    help="attn-prefill: the table over an FP8 KV cache")
     a = ap.parse_args()
     {"bn": bench_bn, "bn-tune": bench_bn_tune, "conv1x1": bench_conv1x1, "conv1x1-own": bench_conv1x1_own, "conv1x1-stats": bench_conv1x1_stats, "wgrad-o1": bench_wgrad_o1, "wgrad-dense": bench_wgrad_dense, "optim": bench_optim,
      "ln": bench_ln, "ln-join": bench_ln_join, "conv-bnbwd": bench_conv_bnbwd, "lamb": bench_lamb, "wgrad": bench_wgrad,
